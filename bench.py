@@ -82,10 +82,36 @@ def parse():
                          "default N=1 line carries under `c3` (a child process: python bench.py --config c3 --steps 20 --warmup 5)")
     ap.add_argument("--no-precision-modes", action="store_true",
                     help="skip the short extra runs of the opt-in conv arithmetic modes (reported under precision_modes, N=1 only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the LAST timed step computed (rank 0) as DIR/<name>.npy, float32: loss, logits, "
+                         "and the flat parameters / gradients after the optimizer step (c5: the inferred volume). Arrays above "
+                         f"{DUMP_MAX_ELEMS} elements are a fixed seeded sample of that many elements (same indices every run), "
+                         "so two builds can be compared output for output")
     # TEST INFRASTRUCTURE (tests/test_bench_contract.py): run the launch / rank / reduce plumbing of this script on the CPU emulator
     # build of the kernel sources over gloo. Never a measurement: the line it prints says so in "data".
     ap.add_argument("--emulator-plumbing-test", action="store_true", help=argparse.SUPPRESS)
     return ap.parse_args()
+
+
+DUMP_MAX_ELEMS = 1 << 22          # per array: 16 MiB of float32; at most three such arrays plus the loss stay under 64 MB
+
+
+def dump_sample(t):
+    """`t` as float32 on the host; above DUMP_MAX_ELEMS elements, the elements of the flattened tensor at a fixed seeded set of indices
+    (ascending)."""
+    t = t.detach()
+    if t.numel() > DUMP_MAX_ELEMS:
+        idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_MAX_ELEMS].sort().values
+        t = t.reshape(-1)[idx.to(t.device)]
+    return t.float().cpu().numpy()
+
+
+def dump_outputs(d, arrays):
+    """Writes {name: tensor} as d/<name>.npy (float32; see dump_sample). Called once, after the timed region."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), dump_sample(t).astype(np.float32))
 
 
 def _free_port():
@@ -301,9 +327,11 @@ def bench_c5(args, unet, inferer_mod, dev):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            inf(x, m)
+            out = inf(x, m)
         torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / args.steps
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"output": out})
     return {"metric": "sliding-window inference volumes/sec (240x240x155, 128^3 windows)", "value": round(1.0 / dt, 4), "unit": "volumes/s",
             "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt * 1e3, 3), "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None, "dtype": DTYPE[args.precision], "data": "synthetic",
@@ -408,9 +436,13 @@ def main():
     # which a throughput line should not time (the GradScaler protocol itself: tests/test_boundary.py)
     scaler = 65536.0 if args.storage == "fp16" else None
 
+    last_logits = []                                              # --dump-outputs: the logits of the latest step
+
     def eager_step():
         optimizer.zero_grad(set_to_none=True)
         out = model(x)
+        if args.dump_outputs:
+            last_logits[:] = [out]
         loss = criterion(out, y)
         if scaler is not None:
             (loss * scaler).backward()
@@ -461,6 +493,20 @@ def main():
     dt = time.perf_counter() - t0
     prof_timed, be.prof = be.prof, None
     loss_val = float(loss.item())
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed its caller, read before any further step: the loss, the logits, and the parameters and their
+        # gradients as the optimizer step left them (flat, in model.parameters() order)
+        if graphed is not None and graphed.graph is not None:
+            last_logits[:] = [graphed.logits]
+        params = list(model.parameters())
+        dumped = {"loss": loss.reshape(1)}
+        if last_logits:
+            dumped["logits"] = last_logits[0]
+        dumped["parameters"] = torch.cat([p.detach().reshape(-1) for p in params])
+        dumped["gradients"] = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1) for p in params])
+        dump_outputs(args.dump_outputs, dumped)
+        del dumped
+    last_logits.clear()
     # Host enqueue time of one step, measured OUTSIDE the timed region on an idle device: inside it a GPU-bound loop runs the host into
     # the launch queue's depth limit, and the time spent blocked there says nothing about the Python / launch work of a step.
     host_s[0], host_s[1] = 0.0, 0

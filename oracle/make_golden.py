@@ -7,8 +7,10 @@ Contents: constructor kwargs, the reference's state_dict under seed 1234, a synt
 the reference's logits (eval mode: Dropout3d off, myronenko.py:70-79), sigmoid-Dice loss (oracle/torch_ops.py) and every
 parameter gradient -- fp32 CPU.
 """
+import importlib
 import os
 import sys
+import types
 
 import torch
 
@@ -55,6 +57,130 @@ def make_autocast(path, bundle_path):
     print(path, os.path.getsize(path) // 1024, "KiB")
 
 
+# The checks tests/ used to run against the imported reference, recorded once (tests/golden/reference_checks.pt): the suite then needs
+# nothing outside the repository. The cases are the ones the tests name; the tests assert the same conditions on the recorded values.
+LIVE_CASES = [(dict(n_features=4, n_outputs=3, base_width=8), (16, 16, 16)),
+              (dict(n_features=4, n_outputs=3, base_width=8, encoder_blocks=[1, 1, 2], use_transposed_convolutions=True), (12, 16, 8)),
+              (dict(n_features=4, n_outputs=3, base_width=8, encoder_blocks=[1, 2, 1]), (15, 13, 10))]     # odd sizes: crop path
+INIT_CASES = [dict(n_features=4, n_outputs=3), dict(n_features=4, n_outputs=3, use_transposed_convolutions=True),
+              dict(n_features=4, n_outputs=3, base_width=16, encoder_blocks=[1, 2, 2, 2, 4])]
+TILE_KW = dict(n_features=4, n_outputs=3, base_width=8, encoder_blocks=[1, 1, 1])          # tests/test_boundary.py KW
+
+
+# Floating-point results are kept as a fixed seeded sample of their elements plus whole-tensor summaries (max |x|, sum |x|, L2 norm);
+# results that must match bit for bit (initialisations, checkpoints, integer label maps) as sha256 digests. The fixture stays small.
+GRAD_SAMPLE = 32
+LOGIT_SAMPLE = 1024
+
+
+def sample_index(numel, k):
+    """The elements of a flattened tensor a fixture keeps: all of a small tensor, else a fixed seeded k of them (ascending)."""
+    if numel <= k:
+        return torch.arange(numel)
+    return torch.randperm(numel, generator=torch.Generator().manual_seed(0))[:k].sort().values
+
+
+def summary(t):
+    """float64 [max |x|, sum |x|, L2 norm] of the whole tensor."""
+    t = t.detach().double().reshape(-1)
+    return torch.tensor([float(t.abs().max()), float(t.abs().sum()), float(t.norm())], dtype=torch.float64)
+
+
+def sampled(t, k):
+    """{sample at sample_index(numel, k), summary}."""
+    flat = t.detach().reshape(-1)
+    return {"shape": tuple(t.shape), "sample": flat[sample_index(flat.numel(), k)].clone(), "summary": summary(flat)}
+
+
+def key_digests(sd):
+    """{key: the first 16 hex digits of its tensor's digest}, in key order: names the tensor that differs, at 64 bits per key."""
+    return {k: torch_ops.tensor_digest(v)[:16] for k, v in sd.items()}
+
+
+def state_dict_digest(sd):
+    """One sha256 over a state_dict's keys (in order) and the digests of its tensors."""
+    import hashlib
+    return hashlib.sha256("".join(f"{k}={torch_ops.tensor_digest(v)};" for k, v in sd.items()).encode()).hexdigest()
+
+
+def _reference_one_hot_module():
+    reference_shim.import_reference_unet()
+    if "monai.data" not in sys.modules:
+        md = types.ModuleType("monai.data")
+
+        class MetaTensor(torch.Tensor):        # minimal stand-in: a Tensor subclass that survives torch ops and has `.meta`
+            meta = {}
+
+            @staticmethod
+            def __new__(cls, x, meta=None, **kw):
+                return torch.Tensor._make_subclass(cls, x)
+        md.MetaTensor = MetaTensor
+        sys.modules["monai.data"] = md
+        sys.modules["monai"].data = md
+    return importlib.import_module("unet3d.utils.one_hot")
+
+
+def make_reference_checks(path):
+    unet = importlib.import_module("3dunetcnn_amd.unet")
+    out = {"generator": "oracle/make_golden.py make_reference_checks: the reference's UNet3D, unet3d.utils.one_hot and "
+                        "unet3d.models.build, torch " + torch.__version__ + " CPU fp32"}
+    # tests/test_oracle_pinned.py test_oracle_matches_live_reference: logits and parameter gradients of the reference at seed 11
+    live = []
+    for kw, dhw in LIVE_CASES:
+        ref = reference_shim.build_reference_unet3d(seed=11, **kw).eval()
+        x, y = unet3d_ref.synthetic_case(2, 4, dhw)
+        want = ref(x)
+        torch_ops.dice_loss(want, y).backward()
+        keys = [k for k, p in ref.named_parameters()]
+        grads = [sampled(p.grad, GRAD_SAMPLE) for _, p in ref.named_parameters()]
+        live.append({"kwargs": kw, "dhw": dhw, "state_dict_sha256": state_dict_digest(ref.state_dict()), "logits": sampled(want, LOGIT_SAMPLE),
+                     "grad_keys": keys, "grad_samples": torch.cat([g["sample"] for g in grads]),
+                     "grad_summaries": torch.stack([g["summary"] for g in grads])})
+    out["live_cases"] = live
+    # test_state_dict_contract_and_same_seed_init: the reference's state_dict keys (in order), shapes, dtypes and default init at seed 1234
+    out["init_cases"] = []
+    for kw in INIT_CASES:
+        sd = reference_shim.build_reference_unet3d(seed=1234, **kw).state_dict()
+        out["init_cases"].append({"kwargs": kw, "sha256": key_digests(sd)})      # keys in order; a digest covers dtype, shape and values
+    # tests/test_input_channels.py test_empty_batch_matches_reference_behaviour: the reference's output shape on an empty batch
+    ref = reference_shim.build_reference_unet3d(n_features=4, n_outputs=3, base_width=8, encoder_blocks=[1, 1]).eval()
+    out["empty_batch_logits_shape"] = tuple(ref(torch.zeros(0, 4, 8, 8, 8)).shape)
+    # tests/test_prepost.py test_oracle_matches_live_reference_functions: the reference's one-hot encode / decode on seeded inputs
+    ref = _reference_one_hot_module()
+    g = torch.Generator().manual_seed(0)
+    lm = torch.randint(0, 5, (1, 1, 9, 8, 7), generator=g).float()
+    enc = [(labels, ref.compile_one_hot_encoding(sys.modules["monai.data"].MetaTensor(lm), 3 if labels is None else len(labels),
+                                                 labels=labels).as_subclass(torch.Tensor).clone())
+           for labels in ([1, 2, 4], [[1, 2], [4]], None)]
+    oh = torch.rand(3, 9, 8, 7, generator=g)
+    dec = [(labels, kw, ref.convert_one_hot_to_label_map(oh, labels, **kw).clone())
+           for labels, kw in (([2, 1, 4], dict(label_hierarchy=True)), ([2, 1, 4], dict()), ([2, 1, 4], dict(sum_then_threshold=True)),
+                              ([2, 1, 4], dict(threshold=0.7)), ([[2, 1], [4]], dict()))]
+    out["one_hot"] = {"label_map_sha256": torch_ops.tensor_digest(lm), "one_hot_sha256": torch_ops.tensor_digest(oh),
+                      "encode": [(labels, torch_ops.tensor_digest(t)) for labels, t in enc],
+                      "decode": [(labels, kw, torch_ops.tensor_digest(t)) for labels, kw, t in dec]}
+    # tests/test_boundary.py test_reference_loader_tiles_a_narrower_checkpoint: the reference loader's match_state_dict_shapes applied to a
+    # narrower HipUNet3D checkpoint (seed 3, half the input modalities and half the widths) for a TILE_KW model
+    build = importlib.import_module("unet3d.models.build")
+    torch.manual_seed(3)
+    narrow = unet.HipUNet3D(**{**TILE_KW, "n_features": 2, "base_width": 4}).state_dict()
+    tiled = build.match_state_dict_shapes(unet.HipUNet3D(**TILE_KW).state_dict(), {k: v.clone() for k, v in narrow.items()})
+    out["tiled_checkpoint"] = {"kwargs": TILE_KW, "narrow_seed": 3, "narrow_sha256": state_dict_digest(narrow),
+                               "tiled_sha256": key_digests(tiled)}
+    torch.save(out, path)
+    print(path, os.path.getsize(path) // 1024, "KiB")
+
+
+def make_brats_config(path):
+    """The `model` section of the reference's examples/brats2020/brats2020_config.json (the DynUNet configuration HipDynUNet takes)."""
+    import json
+    cfg = json.load(open(os.path.join(reference_shim.REFERENCE_ROOT, "examples", "brats2020", "brats2020_config.json")))
+    with open(path, "w") as f:
+        json.dump({"model": cfg["model"]}, f, indent=1)
+        f.write("\n")
+    print(path)
+
+
 if __name__ == "__main__":
     out = os.path.join(ROOT, "tests", "golden")
     os.makedirs(out, exist_ok=True)
@@ -62,3 +188,5 @@ if __name__ == "__main__":
     make(os.path.join(out, "unet3d_small_transposed.pt"),
          dict(n_features=4, n_outputs=3, base_width=8, encoder_blocks=[1, 1, 1], use_transposed_convolutions=True), (16, 16, 16), 1)
     make_autocast(os.path.join(out, "unet3d_small_autocast.pt"), os.path.join(out, "unet3d_small.pt"))
+    make_reference_checks(os.path.join(out, "reference_checks.pt"))
+    make_brats_config(os.path.join(out, "brats2020_config_model.json"))

@@ -129,3 +129,12 @@ def adam_step(p, g, m, v, lr, b1, b2, eps, wd, step):
     denom = (v.sqrt() / (bc2 ** 0.5)).add_(eps)
     p.addcdiv_(m, denom, value=-lr / bc1)
     return p
+
+
+def tensor_digest(t):
+    """sha256 of a tensor's dtype, shape and bytes: pins a tensor (an initialisation, a checkpoint) in a golden fixture without storing it."""
+    import hashlib
+    t = t.detach().cpu().contiguous()
+    h = hashlib.sha256(f"{t.dtype} {tuple(t.shape)}".encode())
+    h.update(t.view(torch.uint8).numpy().tobytes() if t.numel() else b"")
+    return h.hexdigest()

@@ -283,3 +283,41 @@ def test_c3_block_keeps_the_figures_of_the_child_line(monkeypatch):
     R.returncode = 3
     blk = b.c3_block()
     assert "error" in blk and "exited 3" in blk["error"]
+
+
+def test_dump_outputs_writes_the_last_timed_step(emu_backend, tmp_path):
+    """--dump-outputs DIR: after the timed steps, the loss, logits, parameters and gradients of the LAST timed step as float32 .npy files
+    (under 64 MB in all), the same for the same arguments from run to run (emulator plumbing run). The loss is the line's final_loss, and
+    --steps sets the number of timed steps: one step more moves the parameters on."""
+    import numpy as np
+    env = dict(os.environ, RANK="0", LOCAL_RANK="0", WORLD_SIZE="1")
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--size", "8", "--batch", "1", "--warmup", "1",
+            "--emulator-plumbing-test"]
+    runs = {}
+    for tag, steps in (("a", 2), ("b", 2), ("c", 3)):
+        p = subprocess.run(base + ["--steps", str(steps), "--dump-outputs", str(tmp_path / tag)], capture_output=True, text=True, env=env,
+                           timeout=900)
+        assert p.returncode == 0, p.stderr[-2000:]
+        line = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][0])
+        assert line["steps"] == steps and line["ms_per_step"] > 0
+        files = sorted(f for f in os.listdir(tmp_path / tag))
+        assert files == ["gradients.npy", "logits.npy", "loss.npy", "parameters.npy"], files
+        arrays = {f[:-4]: np.load(tmp_path / tag / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in arrays.values())
+        assert sum(os.path.getsize(tmp_path / tag / f) for f in files) < 64e6
+        assert arrays["logits"].shape == (1, 3, 8, 8, 8) and arrays["parameters"].shape == arrays["gradients"].shape
+        assert abs(float(arrays["loss"][0]) - line["final_loss"]) < 1e-5
+        runs[tag] = arrays
+    for k in runs["a"]:
+        assert np.array_equal(runs["a"][k], runs["b"][k]), k
+    assert not np.array_equal(runs["a"]["parameters"], runs["c"]["parameters"])
+
+
+def test_dump_sample_is_fixed_and_bounded():
+    import torch
+    b = _bench()
+    t = torch.arange(b.DUMP_MAX_ELEMS + 5, dtype=torch.float64)
+    s1, s2 = b.dump_sample(t), b.dump_sample(t.clone())
+    assert s1.dtype.name == "float32" and s1.shape == (b.DUMP_MAX_ELEMS,) and (s1 == s2).all() and (s1[1:] > s1[:-1]).all()
+    small = torch.randn(2, 3, 4)
+    assert b.dump_sample(small).shape == (2, 3, 4)

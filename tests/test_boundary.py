@@ -1,13 +1,15 @@
 """The drop-in boundary's edges (SURVEY.md 8b "object protocol"): what the reference's builder / loader / training loop may do with
 the module besides calling it -- DataParallel wrap, tolerant checkpoint loading, frozen parameters, odd constructor kwargs -- and
 that each case either works like the reference or fails loudly, never silently.
-Kernels run on the CPU emulator (test infrastructure); /root/reference is imported where the reference's own code is the caller."""
+Kernels run on the CPU emulator (test infrastructure); where the reference's own code is the caller, its results are recorded under
+tests/golden/ (oracle/make_golden.py)."""
 import importlib
+import os
 
 import pytest
 import torch
 
-from oracle import reference_shim, torch_ops as O, unet3d_ref as R
+from oracle import make_golden, torch_ops as O, unet3d_ref as R
 
 unet = importlib.import_module("3dunetcnn_amd.unet")
 losses = importlib.import_module("3dunetcnn_amd.losses")
@@ -49,20 +51,35 @@ def test_data_parallel_wrap_on_one_gpu_runs_the_module_itself(hip_backend):
             torch.nn.parallel.replicate(m, [0, 0])[1](x.cuda())
 
 
-@pytest.mark.skipif(not reference_shim.available(), reason="/root/reference only exists in the build container")
-def test_reference_loader_tiles_a_narrower_checkpoint(emu_backend, tmp_path):
+def _tile_to(t, shape):
+    """A narrower tensor repeated along every dimension where it is too short, then cropped to `shape` (what the reference's loader
+    does to each mismatched tensor; the result is pinned to the reference's own by digest below)."""
+    for d, n in enumerate(shape):
+        if t.shape[d] < n:
+            reps = [1] * t.dim()
+            reps[d] = -(-n // t.shape[d])
+            t = t.repeat(*reps)
+        t = t.narrow(d, 0, n)
+    return t
+
+
+def test_reference_loader_tiles_a_narrower_checkpoint(emu_backend):
     """unet3d/models/build.py:47-64 (match_state_dict_shapes / match_tensor_sizes): with strict=False a checkpoint whose tensors are
     narrower is tiled (torch.cat of copies) and cropped to the model's shapes before load_state_dict. The module must take that
-    state_dict like an nn.Module made of torch layers does: same keys, OIDHW shapes, and the flat buffer must follow the loaded values."""
-    reference_shim.import_reference_unet()
-    importlib.import_module("3dunetcnn_amd.register").register()
-    build = importlib.import_module("unet3d.models.build")
-    torch.manual_seed(3)
+    state_dict like an nn.Module made of torch layers does: same keys, OIDHW shapes, and the flat buffer must follow the loaded values.
+    The tiled state_dict is checked against digests of the reference loader's own result (oracle/make_golden.py) for the narrow
+    checkpoint below, and handed to load_state_dict(strict=False) as that loader does (build.py:33-37)."""
+    rec = torch.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_checks.pt"))["tiled_checkpoint"]
+    assert rec["kwargs"] == KW
+    torch.manual_seed(rec["narrow_seed"])
     narrow = unet.HipUNet3D(**{**KW, "n_features": 2, "base_width": 4})         # half the input modalities and half the widths
-    path = str(tmp_path / "narrow.pth")
-    torch.save(narrow.state_dict(), path)
-    model = build.build_or_load_model("HipUNet3D", path, n_gpus=0, strict=False, **KW)
-    want = build.match_state_dict_shapes(unet.HipUNet3D(**KW).state_dict(), torch.load(path))
+    assert make_golden.state_dict_digest(narrow.state_dict()) == rec["narrow_sha256"]
+    model = unet.HipUNet3D(**KW)
+    shapes = {k: v.shape for k, v in model.state_dict().items()}
+    want = {k: _tile_to(v, shapes[k]).clone() for k, v in narrow.state_dict().items()}
+    assert make_golden.key_digests(want) == rec["tiled_sha256"]
+    model.load_state_dict({k: v.clone() for k, v in want.items()}, strict=False)
+    assert list(model.state_dict()) == list(want)
     for k, v in model.state_dict().items():
         assert v.shape == want[k].shape and torch.equal(v, want[k]), k
     w = model.state_dict()["encoder.layers.0.blocks.0.conv1.conv.weight"]       # (8, 4, 3, 3, 3) tiled from (4, 2, 3, 3, 3)

@@ -2,6 +2,7 @@
 zero-padded to a float4 multiple, the first block's parameters as zero-padded copies; logits, loss, every parameter gradient
 and the input gradient must match the CPU oracle graph (1e-3 relative, BASELINE north star)."""
 import importlib
+import os
 
 import pytest
 import torch
@@ -99,7 +100,7 @@ def test_odd_input_channels_gpu(cin):
 
 def test_empty_batch_matches_reference_behaviour(emu_backend):
     """N = 0: the reference's Conv3d / GroupNorm stack returns an empty [0, n_outputs, D, H, W] tensor and backward gives
-    zero gradients (checked live on /root/reference when it is present); the HIP modules launch nothing and do the same."""
+    zero gradients (the reference's output shape as recorded in tests/golden/reference_checks.pt); the HIP modules launch nothing and do the same."""
     import importlib
     unet = importlib.import_module("3dunetcnn_amd.unet")
     dyn = importlib.import_module("3dunetcnn_amd.dynunet")
@@ -112,7 +113,6 @@ def test_empty_batch_matches_reference_behaviour(emu_backend):
         assert tuple(y.shape) == (0, 3, 8, 8, 8) and y.requires_grad
         y.sum().backward()
         assert all(p.grad is not None and float(p.grad.abs().sum()) == 0.0 for p in m.parameters())
-    from oracle import reference_shim as S
-    if S.available():
-        ref = S.build_reference_unet3d(n_features=4, n_outputs=3, base_width=8, encoder_blocks=[1, 1]).eval()
-        assert tuple(ref(torch.zeros(0, 4, 8, 8, 8)).shape) == (0, 3, 8, 8, 8)
+    # the reference's own output shape on the empty batch, recorded by oracle/make_golden.py
+    ref = torch.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_checks.pt"))
+    assert tuple(ref["empty_batch_logits_shape"]) == (0, 3, 8, 8, 8)

@@ -1,33 +1,15 @@
 """Steps either side of the network: on-device one-hot encode, label-map decode (+ activation) and intensity
-normalisation vs oracle/prepost_ref.py, which is itself pinned here against the reference's live functions and against the
+normalisation vs oracle/prepost_ref.py, which is itself pinned here against the reference's functions (their recorded results) and against the
 known answers of the reference's own tests."""
 import importlib
-import sys
-import types
+import os
 
 import pytest
 import torch
 
-from oracle import prepost_ref as P, reference_shim
+from oracle import prepost_ref as P, torch_ops as O
 
 prepost = importlib.import_module("3dunetcnn_amd.prepost")
-
-
-def _reference_one_hot_module():
-    reference_shim.import_reference_unet()
-    if "monai.data" not in sys.modules:
-        md = types.ModuleType("monai.data")
-
-        class MetaTensor(torch.Tensor):        # minimal stand-in: a Tensor subclass that survives torch ops and has `.meta`
-            meta = {}
-
-            @staticmethod
-            def __new__(cls, x, meta=None, **kw):
-                return torch.Tensor._make_subclass(cls, x)
-        md.MetaTensor = MetaTensor
-        sys.modules["monai.data"] = md
-        sys.modules["monai"].data = md
-    return importlib.import_module("unet3d.utils.one_hot")
 
 
 def _label_volume():
@@ -54,20 +36,24 @@ def test_oracle_reproduces_the_reference_tests_known_answers():
     assert torch.equal(P.convert_one_hot_to_label_map(torch.stack((left, right)), [3, 17]), lm)
 
 
-@pytest.mark.skipif(not reference_shim.available(), reason="/root/reference only exists in the build container")
 def test_oracle_matches_live_reference_functions():
-    ref = _reference_one_hot_module()
+    """The reference's compile_one_hot_encoding / convert_one_hot_to_label_map on seeded inputs: digests of its results (dtype, shape
+    and values), recorded by oracle/make_golden.py."""
+    ref = torch.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_checks.pt"))["one_hot"]
     g = torch.Generator().manual_seed(0)
     lm = torch.randint(0, 5, (1, 1, 9, 8, 7), generator=g).float()
-    lm_meta = sys.modules["monai.data"].MetaTensor(lm)
-    for labels in ([1, 2, 4], [[1, 2], [4]], None):
+    assert O.tensor_digest(lm) == ref["label_map_sha256"]
+    assert [labels for labels, _ in ref["encode"]] == [[1, 2, 4], [[1, 2], [4]], None]
+    for labels, want in ref["encode"]:
         n = 3 if labels is None else len(labels)
-        want = ref.compile_one_hot_encoding(lm_meta, n, labels=labels).as_subclass(torch.Tensor)
-        assert torch.equal(want, P.compile_one_hot_encoding(lm, n, labels=labels))
+        assert O.tensor_digest(P.compile_one_hot_encoding(lm, n, labels=labels)) == want, labels
     oh = torch.rand(3, 9, 8, 7, generator=g)
-    for kw in (dict(label_hierarchy=True), dict(), dict(sum_then_threshold=True), dict(threshold=0.7)):
-        assert torch.equal(ref.convert_one_hot_to_label_map(oh, [2, 1, 4], **kw), P.convert_one_hot_to_label_map(oh, [2, 1, 4], **kw))
-    assert torch.equal(ref.convert_one_hot_to_label_map(oh, [[2, 1], [4]]), P.convert_one_hot_to_label_map(oh, [[2, 1], [4]]))
+    assert O.tensor_digest(oh) == ref["one_hot_sha256"]
+    assert [(labels, kw) for labels, kw, _ in ref["decode"]] == [([2, 1, 4], dict(label_hierarchy=True)), ([2, 1, 4], dict()),
+                                                                 ([2, 1, 4], dict(sum_then_threshold=True)), ([2, 1, 4], dict(threshold=0.7)),
+                                                                 ([[2, 1], [4]], dict())]
+    for labels, kw, want in ref["decode"]:
+        assert O.tensor_digest(P.convert_one_hot_to_label_map(oh, labels, **kw)) == want, (labels, kw)
 
 
 def _cases(dev, be, dhw):
