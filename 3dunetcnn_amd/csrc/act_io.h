@@ -94,6 +94,10 @@ static inline uintptr_t act_align_mask(int dtype) { return act_is_lp16(dtype) ? 
 static inline bool act_matches_precision(int dtype, int precision) {
   return dtype == MI355_ACT_F32 || (dtype == MI355_ACT_BF16 && precision == MI355_PREC_BF16) || (dtype == MI355_ACT_F16 && precision == MI355_PREC_F16);
 }
+// operand planes of a 16-bit precision mode (bf16x3: 2, bf16x6: 3, bf16 / fp16: 1); 0: not one
+static inline int lp_nsplit(int precision) {
+  return precision == MI355_PREC_BF16X3 ? 2 : precision == MI355_PREC_BF16X6 ? 3 : (precision == MI355_PREC_BF16 || precision == MI355_PREC_F16);
+}
 // a view the streaming kernels accept: 4-element (float4 / 8-byte) granularity
 static inline int act_view_ok(const mi355_act* t) {
   return t && t->p && act_dtype_ok(t) && t->c > 0 && t->c % 4 == 0 && t->ld % 4 == 0 && t->ld >= t->c &&

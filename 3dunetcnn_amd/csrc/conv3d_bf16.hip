@@ -438,10 +438,11 @@ void conv3d_k3_bf16(ConvBArgs a) {
 // shape: tests), zring1 (the round-3 kernel where it applies: the A/B switch), tile (never).
 // Measured: profiles/r3_bf16_zring.txt (zring1), profiles/r4_bf16_zring2.txt (zring2).
 struct LpZPlan { int tilesY, tilesX, zsplits, zper, use, ks, coTiles; };
-static LpZPlan plan_lp_zring(int n, int cin, int cout, int d, int h, int w, int precision, const mi355_conv_desc* desc, int act_dtype = MI355_ACT_F32) {
+// fe, ze: the values of MI355_BF16_FORM and MI355_BF16_ZSPLITS (plan_lp reads them)
+static LpZPlan plan_lp_zring(int n, int cin, int cout, int d, int h, int w, int precision, const mi355_conv_desc* desc, int act_dtype,
+                             const char* fe, const char* ze) {
   LpZPlan p; memset(&p, 0, sizeof(p));
   if (!act_matches_precision(act_dtype, precision)) return p;      // 16-bit storage goes with operands of its own type
-  const char* fe = getenv("MI355_BF16_FORM");
   const bool v1 = fe && !strncmp(fe, "zring1", 6);
   const char form = fe && fe[0] ? fe[0] : 'a';
   if (form != 'z' && form != 'a') return p;
@@ -449,8 +450,7 @@ static LpZPlan plan_lp_zring(int n, int cin, int cout, int d, int h, int w, int 
   if (cin % 4 || h % 8 || w % 16 || d < 1) return p;
   if (desc->pad != 1 || desc->off_z || desc->off_y || desc->off_x || desc->out_d != d || desc->out_h != h || desc->out_w != w) return p;
   p.tilesY = h / 8; p.tilesX = w / 16;
-  const long long cols = (long long)n * p.tilesY * p.tilesX;
-  const char* ze = getenv("MI355_BF16_ZSPLITS");            // tests: force the number of z ranges
+  const long long cols = (long long)n * p.tilesY * p.tilesX;      // (ze, tests: force the number of z ranges)
   // Norm-backward sums in the epilogue (desc->gn_bwd): conv3d_k3_lp_zring2 has no such form. On 33..64 input channels the normalised
   // tensor's 16 values per lane do not fit beside 216 weight and 96 accumulator registers (140 spills); the 32-channel instantiation
   // compiled clean and ran correctly on the CPU emulator but faulted on the MI355X (HSA memory aperture violation on the loads of the
@@ -502,18 +502,8 @@ __global__ void pack_weight_bf16_kernel(const float* w, unsigned short* wp, int 
     pack_lp_item(w, wp, idx, cout, cin, T, coutP, cinP, mode, NS, f16);      // pack_values.h (shared with mi355_pack_weights_batch)
 }
 
-static int nsplit_of(int precision) {
-  switch (precision) {
-    case MI355_PREC_BF16X3: return 2;
-    case MI355_PREC_BF16X6: return 3;
-    case MI355_PREC_BF16: return 1;
-    case MI355_PREC_F16: return 1;
-    default: return 0;
-  }
-}
-
 extern "C" size_t mi355_packed_weight_bytes_bf16(int32_t cout, int32_t cin, int32_t kd, int32_t precision) {
-  const int ns = nsplit_of(precision);
+  const int ns = lp_nsplit(precision);
   if (!ns) return 0;
   const int coutP = (cout + 31) / 32 * 32, cinP = (cin + 15) / 16 * 16;
   return (size_t)kd * kd * kd * cinP * coutP * ns * 2;
@@ -521,7 +511,7 @@ extern "C" size_t mi355_packed_weight_bytes_bf16(int32_t cout, int32_t cin, int3
 
 extern "C" int mi355_pack_conv_weight_bf16(const float* w, void* wp, int32_t cout, int32_t cin, int32_t kd, int32_t mode,
                                            int32_t precision, void* stream) {
-  const int ns = nsplit_of(precision);
+  const int ns = lp_nsplit(precision);
   if (!w || !wp || cout <= 0 || cin <= 0 || kd != 3 || mode < 0 || mode > 1 || !ns) return MI355_EINVAL;
   const int coutP = (cout + 31) / 32 * 32, cinP = (cin + 15) / 16 * 16;
   const size_t total = (size_t)27 * cinP * coutP;
@@ -569,14 +559,14 @@ static int launch_b(ConvBArgs& a, int in_mode, void* stream) {
 // their kernels carry the interior epilogue alone; with the general one beside 128 accumulators hipcc spills 265
 // registers and the call ran slower, 0.136 -> 0.185 ms). The small wide form is not routed there: interior-only it fits three waves per
 // SIMD (168 registers, 219 with the general epilogue) and still measured 0.111 against 0.107 ms on 256 -> 256 @16^3 (the 64-channel form).
-// MI355_BF16_WIDE: 0 = never, big / small = that wide form on every eligible call whatever its size (tests), otherwise by size.
+// e = MI355_BF16_WIDE (plan_lp reads it): 0 = never, big / small = that wide form on every eligible call whatever its size (tests), otherwise
+// by size.
 struct LpTileCfg { bool big; int nw; };      // nw: output channels per workgroup (32, 64, 128)
 static int lp_whole(int d, int h, int w) { return (h % 4 == 0 && w % 16 == 0) ? (d % 4 == 0 ? 3 : (d % 2 == 0 ? 2 : 0)) : 0; }      // bit 0: whole 4 x 4 x 16 tiles, bit 1: whole 2 x 4 x 16
-static LpTileCfg lp_tile_cfg(int ns, long long vox, int cout, bool gnb, int whole) {
+static LpTileCfg lp_tile_cfg(int ns, long long vox, int cout, bool gnb, int whole, const char* e) {
   LpTileCfg c;
   c.big = ns < 3 && vox >= 256LL * 512;      // the 3-plane tile of the big configuration would exceed the 64 KiB LDS window
   c.nw = cout > 32 ? 64 : 32;
-  const char* e = getenv("MI355_BF16_WIDE");
   if (ns == 1 && cout % 128 == 0 && !(e && e[0] == '0')) {
     const bool fb = e && e[0] == 'b', fs = e && e[0] == 's';
     if (gnb) {
@@ -589,9 +579,8 @@ static LpTileCfg lp_tile_cfg(int ns, long long vox, int cout, bool gnb, int whol
 }
 
 template <int NS, bool F16 = false, typename TA = float>
-static int dispatch_ns(ConvBArgs& a, int in_mode, long long vox, void* stream) {
+static int dispatch_ns(ConvBArgs& a, int in_mode, const LpTileCfg& c, void* stream) {
   constexpr int J = NS == 1 ? 2 : 1;      // (one 16-channel k-step per chunk for NS = 1 too: more workgroups per CU, measured 10 % slower)
-  const LpTileCfg c = lp_tile_cfg(NS, vox, a.Cout, a.g.gnb != nullptr, lp_whole(a.Do, a.Ho, a.Wo));
   if constexpr (NS < 3) {
     if (c.big) {
       if constexpr (NS == 1)
@@ -606,70 +595,66 @@ static int dispatch_ns(ConvBArgs& a, int in_mode, long long vox, void* stream) {
   return launch_b<2, 4, J, NS, 4, 1, 1, 1, F16, TA>(a, in_mode, stream);
 }
 
-// spatial tiles (= epilogue records per sample) of the configuration dispatch_ns picks; 0: this call cannot fuse statistics
-int32_t mi355_conv3d_bf16_stats_blocks(const mi355_act* x, const mi355_act* y, const mi355_conv_desc* d) {
-  const int ns = nsplit_of(d->precision);
-  if (!ns || d->kd != 3 || d->stride != 1 || d->out_mode != MI355_OUT_PLAIN) return 0;
-  if (d->off_z || d->off_y || d->off_x || d->out_d != y->d || d->out_h != y->h || d->out_w != y->w) return 0;
-  const LpZPlan zp = plan_lp_zring(x->n, x->c, y->c, y->d, y->h, y->w, d->precision, d, x->dtype);
+// The plan of a 16-bit forward call: the plane-ring kernels (zp.use 1 / 2) or the tile kernel (tile), and the statistics records the
+// chosen kernel leaves. mi355_conv3d_bf16_stats_blocks, mi355_conv3d_bf16_kernel_name and mi355_conv3d_fwd_bf16_impl all read this one
+// plan. The MI355_BF16_* switches are read here, per call (tests flip them in-process).
+struct LpPlan { int ns; LpZPlan zp; LpTileCfg tile; int32_t stats_blocks; };
+static LpPlan plan_lp(const mi355_act* x, const mi355_act* y, const mi355_conv_desc* d) {
+  LpPlan p; memset(&p, 0, sizeof(p));
+  p.ns = lp_nsplit(d->precision);
+  if (!p.ns) return p;
+  const int Do = d->out_d, Ho = d->out_h, Wo = d->out_w;
+  p.zp = plan_lp_zring(x->n, x->c, y->c, Do, Ho, Wo, d->precision, d, x->dtype, getenv("MI355_BF16_FORM"), getenv("MI355_BF16_ZSPLITS"));
+  if (y->d != Do || y->h != Ho || y->w != Wo || x->d != Do || x->h != Ho || x->w != Wo) p.zp.use = 0;      // the plane rings write whole volumes
+  if (!p.zp.use)
+    p.tile = lp_tile_cfg(p.ns, (long long)Do * Ho * Wo * x->n, y->c, d->gn_bwd != nullptr, lp_whole(Do, Ho, Wo), getenv("MI355_BF16_WIDE"));
+  // spatial tiles (= epilogue records per sample); 0: this call cannot fuse statistics
+  if (d->kd != 3 || d->stride != 1 || d->out_mode != MI355_OUT_PLAIN || d->off_z || d->off_y || d->off_x || y->d != Do || y->h != Ho || y->w != Wo)
+    return p;
+  long long b;
+  if (p.zp.use == 2 && d->gn_bwd) b = 0;                     // zring2 has no norm-backward form (plan_lp_zring): unfused sums
   // plane-ring kernels: one record per (z range, column); zring2 leaves one per wave and half-wave of the column's workgroup (x 8)
-  if (zp.use && x->d == y->d && x->h == y->h && x->w == y->w) {
-    if (zp.use == 2 && d->gn_bwd) return 0;                  // zring2 has no norm-backward form (plan_lp_zring): unfused sums
-    return (int32_t)((long long)zp.zsplits * zp.tilesY * zp.tilesX * (zp.use == 2 ? 8 : 1));
-  }
-  const long long vox = (long long)y->d * y->h * y->w * x->n;
-  const bool big = lp_tile_cfg(ns, vox, y->c, d->gn_bwd != nullptr, lp_whole(y->d, y->h, y->w)).big;
-  const int tz = big ? 4 : 2, ty = 4;
-  const long long b = (long long)ceil_div(y->d, tz) * ceil_div(y->h, ty) * ceil_div(y->w, 16);
-  return b > 0 && b <= 0x7fffffffLL ? (int32_t)b : 0;
+  else if (p.zp.use) b = (long long)p.zp.zsplits * p.zp.tilesY * p.zp.tilesX * (p.zp.use == 2 ? 8 : 1);
+  else b = (long long)ceil_div(Do, p.tile.big ? 4 : 2) * ceil_div(Ho, 4) * ceil_div(Wo, 16);
+  p.stats_blocks = b > 0 && b <= 0x7fffffffLL ? (int32_t)b : 0;
+  return p;
 }
 
+int32_t mi355_conv3d_bf16_stats_blocks(const mi355_act* x, const mi355_act* y, const mi355_conv_desc* d) { return plan_lp(x, y, d).stats_blocks; }
+
 // Trace name (as rocprofv3 prints it) of the kernel mi355_conv3d_fwd_bf16_impl launches for this call: bench.py keys its per-instantiation
-// roofline rows and the PMC traffic look-up on it (mi355_conv3d_fwd_config). Mirrors the dispatch below.
+// roofline rows and the PMC traffic look-up on it (mi355_conv3d_fwd_config).
 int mi355_conv3d_bf16_kernel_name(const mi355_act* x, const mi355_act* y, const mi355_conv_desc* d, char* out, size_t n) {
-  const int ns = nsplit_of(d->precision);
-  if (!ns || !out || n < 8) return MI355_EINVAL;
+  const LpPlan p = plan_lp(x, y, d);
+  if (!p.ns || !out || n < 8) return MI355_EINVAL;
   const int fuse = d->moments_out ? 1 : (d->gn_bwd ? 2 : 0);
   const char* f16 = d->precision == MI355_PREC_F16 ? "true" : "false";
-  const LpZPlan zp = plan_lp_zring(x->n, x->c, y->c, d->out_d, d->out_h, d->out_w, d->precision, d, x->dtype);
-  if (zp.use && y->d == d->out_d && y->h == d->out_h && y->w == d->out_w && x->d == d->out_d && x->h == d->out_h && x->w == d->out_w) {
-    const char* st = x->dtype == MI355_ACT_BF16 ? "unsigned short" : (x->dtype == MI355_ACT_F16 ? "f16_t" : "float");
-    if (zp.use == 1) snprintf(out, n, "conv3d_k3_lp_zring<2, %d, %d, %s, %s>", d->in_mode, fuse, f16, st);
-    else snprintf(out, n, "conv3d_k3_lp_zring2<2, %d, %d, %d, %s, %s>", zp.ks, d->in_mode, fuse, f16, st);
-    return 0;
+  const char* st = x->dtype == MI355_ACT_BF16 ? "unsigned short" : (x->dtype == MI355_ACT_F16 ? "f16_t" : "float");
+  if (p.zp.use == 1) snprintf(out, n, "conv3d_k3_lp_zring<2, %d, %d, %s, %s>", d->in_mode, fuse, f16, st);
+  else if (p.zp.use == 2) snprintf(out, n, "conv3d_k3_lp_zring2<2, %d, %d, %d, %s, %s>", p.zp.ks, d->in_mode, fuse, f16, st);
+  else {      // WM, WN, MT, NT of dispatch_ns's instantiations, by [big tile][32 / 64 / 128 output channels per workgroup]
+    static const char* const waves[2][3] = {{"4, 1, 1, 1", "2, 2, 2, 1", "2, 2, 2, 2"}, {"4, 1, 2, 1", "4, 1, 2, 2", "2, 2, 4, 2"}};
+    snprintf(out, n, "conv3d_k3_bf16<%d, 4, %d, %d, %s, %d, %d, %s, %s>", p.tile.big ? 4 : 2, p.ns == 1 ? 2 : 1, p.ns, waves[p.tile.big][p.tile.nw / 64],
+             d->in_mode, fuse, f16, st);
   }
-  const long long vox = (long long)d->out_d * d->out_h * d->out_w * x->n;
-  const int J = ns == 1 ? 2 : 1;
-  const LpTileCfg c = lp_tile_cfg(ns, vox, y->c, d->gn_bwd != nullptr, lp_whole(d->out_d, d->out_h, d->out_w));
-  const char* tile = c.big ? (c.nw == 128 ? "4, 4, %d, %d, 2, 2, 4, 2" : c.nw == 64 ? "4, 4, %d, %d, 4, 1, 2, 2" : "4, 4, %d, %d, 4, 1, 2, 1")
-                           : (c.nw == 128 ? "2, 4, %d, %d, 2, 2, 2, 2" : c.nw == 64 ? "2, 4, %d, %d, 2, 2, 2, 1" : "2, 4, %d, %d, 4, 1, 1, 1");
-  char t[64];
-  snprintf(t, sizeof(t), tile, J, ns);
-  snprintf(out, n, "conv3d_k3_bf16<%s, %d, %d, %s, %s>", t, d->in_mode, fuse, f16, x->dtype == MI355_ACT_BF16 ? "unsigned short" : (x->dtype == MI355_ACT_F16 ? "f16_t" : "float"));
   return 0;
 }
 
+int mi355_fill_gn_fuse(GnFuseArgs& g, const mi355_act* x, const mi355_act* y, const mi355_conv_desc* d);      // conv3d_fwd.hip
+
 // called by mi355_conv3d_fwd (conv3d_fwd.hip) when desc->precision selects a bf16 path and the problem qualifies
 int mi355_conv3d_fwd_bf16_impl(const mi355_act* x, const void* wp, const mi355_act* y, const mi355_conv_desc* d, void* stream) {
-  const int ns = nsplit_of(d->precision);
+  const LpPlan p = plan_lp(x, y, d);
+  const int ns = p.ns;
   if (!ns || d->kd != 3 || d->stride != 1) return MI355_EUNSUPPORTED;
   if (d->in_mode != MI355_IN_PLAIN && d->in_mode != MI355_IN_AFFINE_ACT) return MI355_EUNSUPPORTED;
   if (x->dtype != y->dtype) return MI355_EUNSUPPORTED;
   const bool lp = act_is_lp16(x->dtype);
   if (!act_matches_precision(x->dtype, d->precision)) return MI355_EUNSUPPORTED;      // 16-bit storage goes with operands of its own type
   if (lp && (((uintptr_t)y->p & 1) || ((uintptr_t)x->p & 7))) return MI355_EINVAL;
+  if ((d->moments_out || d->gn_bwd) && !p.stats_blocks) return MI355_EUNSUPPORTED;
   ConvBArgs a;
-  memset(&a.g, 0, sizeof(a.g));
-  if (d->moments_out || d->gn_bwd) {
-    if (!mi355_conv3d_bf16_stats_blocks(x, y, d)) return MI355_EUNSUPPORTED;
-    a.g.mom = d->moments_out;
-    if (d->gn_bwd) {
-      const mi355_gn_bwd_fuse* f = d->gn_bwd;
-      if (!f->gx || !f->scale || !f->shift || !f->mean_rstd || !f->partials_out || f->groups <= 0 || y->c % f->groups || f->gx_ld < y->c) return MI355_EINVAL;
-      a.g.gnb = f->partials_out; a.g.gx = (const float*)f->gx; a.g.gxld = f->gx_ld; a.g.gscale = f->scale; a.g.gshift = f->shift; a.g.gmr = f->mean_rstd;
-      a.g.ggroups = f->groups; a.g.gslope = f->act_slope;
-    }
-  }
+  { const int rcg = mi355_fill_gn_fuse(a.g, x, y, d); if (rcg) return rcg; }
   a.x = (const float*)x->p; a.xld = x->ld; a.wp = (const uint4*)wp; a.y = (float*)y->p; a.yld = y->ld;
   a.res = (const float*)d->residual; a.resld = d->residual_ld;
   a.in_scale = d->in_scale; a.in_shift = d->in_shift; a.slope = d->act_slope; a.in_slope = d->in_slope;
@@ -679,9 +664,8 @@ int mi355_conv3d_fwd_bf16_impl(const mi355_act* x, const void* wp, const mi355_a
   a.yD = y->d; a.yH = y->h; a.yW = y->w; a.offz = d->off_z; a.offy = d->off_y; a.offx = d->off_x;
   a.pad = d->pad;
   if (a.res && a.resld < a.Cout) return MI355_EINVAL;
-  const long long vox = (long long)a.Do * a.Ho * a.Wo * a.N;
-  const LpZPlan zp = plan_lp_zring(a.N, a.Cin, a.Cout, a.Do, a.Ho, a.Wo, d->precision, d, x->dtype);
-  if (zp.use && a.yD == a.Do && a.yH == a.Ho && a.yW == a.Wo && a.Di == a.Do && a.Hi == a.Ho && a.Wi == a.Wo) {
+  const LpZPlan& zp = p.zp;
+  if (zp.use) {
     if (a.g.mom && a.g.gnb) return MI355_EUNSUPPORTED;
     if (a.g.gnb && d->in_mode != MI355_IN_PLAIN) return MI355_EUNSUPPORTED;
     a.tilesY = zp.tilesY; a.tilesX = zp.tilesX; a.zsplits = zp.zsplits; a.zper = zp.zper;
@@ -697,10 +681,10 @@ int mi355_conv3d_fwd_bf16_impl(const mi355_act* x, const void* wp, const mi355_a
     }
     return mi355_lp_zring_launch(a, d->in_mode, fuse, f16, lp, blocks, stream);
   }
-  if (x->dtype == MI355_ACT_BF16) return dispatch_ns<1, false, bf16_t>(a, d->in_mode, vox, stream);
-  if (x->dtype == MI355_ACT_F16) return dispatch_ns<1, true, f16_t>(a, d->in_mode, vox, stream);
-  if (d->precision == MI355_PREC_F16) return dispatch_ns<1, true>(a, d->in_mode, vox, stream);
-  if (ns == 1) return dispatch_ns<1>(a, d->in_mode, vox, stream);
-  if (ns == 2) return dispatch_ns<2>(a, d->in_mode, vox, stream);
-  return dispatch_ns<3>(a, d->in_mode, vox, stream);
+  if (x->dtype == MI355_ACT_BF16) return dispatch_ns<1, false, bf16_t>(a, d->in_mode, p.tile, stream);
+  if (x->dtype == MI355_ACT_F16) return dispatch_ns<1, true, f16_t>(a, d->in_mode, p.tile, stream);
+  if (d->precision == MI355_PREC_F16) return dispatch_ns<1, true>(a, d->in_mode, p.tile, stream);
+  if (ns == 1) return dispatch_ns<1>(a, d->in_mode, p.tile, stream);
+  if (ns == 2) return dispatch_ns<2>(a, d->in_mode, p.tile, stream);
+  return dispatch_ns<3>(a, d->in_mode, p.tile, stream);
 }

@@ -684,6 +684,111 @@ extern "C" int mi355_pack_conv_weight(const float* w, float* wp, int32_t cout, i
 }
 
 // ---- dispatch ---------------------------------------------------------------------------------
+// Configuration table of the generic kernel conv3d_mfma (ids are stable; select_cfg picks one, mi355_conv3d_fwd launches the
+// instantiation of the same row, mi355_conv3d_fwd_config prints its template arguments):
+//  0/1: 1x1x1, 256-voxel flat tiles, 64/32 output channels per workgroup
+//  2/3: 3x3x3 stride 2 (also the zero-insert form with stride template 1), 4x4x8 tiles, KC=8
+//  4/5: 3x3x3 stride 1, 4x8x8 tiles, KC=16 (large volumes: >= 131072 output voxels in the batch)
+//  6/7: 3x3x3 stride 1, 2x4x8 / 4x4x8 tiles, KC=32 (small volumes, so the grid still covers 256 CUs)
+//  8:   3x3x3 stride 1, 4x4x8 tiles x 64 output channels, KC=16, 2 M tiles per wave (32768 .. 131071 output voxels, > 32 output
+//       channels: each B fragment feeds two MFMA tiles; +10 % over configuration 6 on the 32^3-level layers)
+struct MfmaCfg { int kc, tiles, tz, ty, tx; const char* args; };      // tiles = MT * NT; args = TZ .. NT as the trace prints them
+static const MfmaCfg kMfmaCfg[9] = {
+    {32, 4, 1, 1, 256, "1, 1, 256, 32, 4, 4, 1, 2, 2"}, {32, 2, 1, 1, 256, "1, 1, 256, 32, 4, 4, 1, 2, 1"},
+    {8, 2, 4, 4, 8, "4, 4, 8, 8, 0, 4, 1, 1, 2"},      {8, 1, 4, 4, 8, "4, 4, 8, 8, 0, 4, 1, 1, 1"},
+    {16, 4, 4, 8, 8, "4, 8, 8, 16, 4, 4, 1, 2, 2"},    {16, 2, 4, 8, 8, "4, 8, 8, 16, 4, 4, 1, 2, 1"},
+    {32, 1, 2, 4, 8, "2, 4, 8, 32, 4, 2, 2, 1, 1"},    {32, 1, 4, 4, 8, "4, 4, 8, 32, 4, 4, 1, 1, 1"},
+    {16, 2, 4, 4, 8, "4, 4, 8, 16, 4, 2, 2, 2, 1"}};
+static int select_cfg(int kd, int stride, long long vox, int cout, int in_mode) {
+  if (kd == 1) return cout > 32 ? 0 : 1;
+  if (stride == 2) return cout > 32 ? 2 : 3;
+  if (vox >= 256LL * 512 || in_mode == MI355_IN_ZERO_INSERT) return cout > 32 ? 4 : 5;   // zero-insert: parity-class tiles need 4x8x8
+  if (cout > 32 && vox >= 64LL * 512) return 8;
+  return cout > 32 ? 6 : 7;
+}
+
+// can this call fuse norm statistics into its epilogue? (plain, un-windowed output: what is stored IS the logical tensor)
+static bool stats_fusable(const mi355_act* x, const mi355_act* y, const mi355_conv_desc* d) {
+  if (!x || !y || !d || d->out_mode != MI355_OUT_PLAIN || d->in_mode == MI355_IN_S2D) return false;
+  if (d->off_z || d->off_y || d->off_x || d->out_d != y->d || d->out_h != y->h || d->out_w != y->w) return false;
+  if ((d->kd != 1 && d->kd != 3) || (d->stride != 1 && d->stride != 2)) return false;
+  return true;
+}
+
+int mi355_conv3d_fwd_bf16_impl(const mi355_act* x, const void* wp, const mi355_act* y, const mi355_conv_desc* d, void* stream);
+int mi355_conv3d_bf16_kernel_name(const mi355_act* x, const mi355_act* y, const mi355_conv_desc* d, char* out, size_t n);
+int32_t mi355_conv3d_bf16_stats_blocks(const mi355_act* x, const mi355_act* y, const mi355_conv_desc* d);
+int mi355_conv3d_c4_ok(const mi355_act* x, const mi355_conv_desc* d);
+int mi355_conv3d_c4_fwd_impl(const mi355_act* x, const float* w, const mi355_act* y, const mi355_conv_desc* d, void* stream);
+int mi355_conv3d_narrow_ok(const mi355_act* x, const mi355_act* y, const mi355_conv_desc* d);
+int mi355_conv3d_narrow_impl(const mi355_act* x, const float* wp, const mi355_act* y, const mi355_conv_desc* d, void* stream);
+// conv3d_s2.hip: the z-marching 32 -> 32 channel stride-2 forward
+int mi355_conv3d_s2c32_ok(const mi355_act* x, const mi355_act* y, const mi355_conv_desc* d);
+int32_t mi355_conv3d_s2c32_stats_blocks(const mi355_act* y);
+int mi355_conv3d_s2c32_fwd_impl(const mi355_act* x, const float* wp, const mi355_act* y, const mi355_conv_desc* d, void* stream);
+int mi355_conv3d_s2c32_dgrad_ok(const mi355_act* x, const mi355_act* y, const mi355_conv_desc* d);
+// conv3d_k1_stream.hip: 1x1x1 forward / data gradient of bf16 tensors as wave streams
+int mi355_conv3d_k1_stream_ok(const mi355_act* x, const mi355_act* y, const mi355_conv_desc* d);
+int mi355_conv3d_k1_stream_impl(const mi355_act* x, const float* wp, const mi355_act* y, const mi355_conv_desc* d, void* stream);
+int mi355_conv3d_s2c32_dgrad_impl(const mi355_act* x, const float* wp, const mi355_act* y, const mi355_conv_desc* d, void* stream);
+
+extern "C" int mi355_conv3d_uses_bf16(const mi355_conv_desc* d) {
+  return d && d->precision != MI355_PREC_F32 && d->kd == 3 && d->stride == 1 &&
+         (d->in_mode == MI355_IN_PLAIN || d->in_mode == MI355_IN_AFFINE_ACT);
+}
+
+// ---- routing: one plan per call -------------------------------------------------------------------
+// mi355_conv3d_fwd launches the route, mi355_conv3d_stats_blocks and mi355_conv3d_fwd_config read it: the three cannot disagree.
+enum FwdRoute { FWD_REFUSED, FWD_C4, FWD_NARROW, FWD_LP16, FWD_S2C32, FWD_S2C32_DGRAD, FWD_K1_STREAM, FWD_MFMA };
+// rc: the status of a refused call; cfg, tl, fullj (FWD_MFMA): row of kMfmaCfg, two-level accumulation, whole channel chunks; fuse: 1 moments
+// epilogue, 2 norm-backward sums; stats_blocks: epilogue records per sample (0: this call cannot fuse statistics)
+struct FwdPlan { FwdRoute route; int rc, cfg; bool tl, fullj; int fuse; int32_t stats_blocks; };
+
+static FwdPlan plan_fwd(const mi355_act* x, const mi355_act* y, const mi355_conv_desc* d) {
+  FwdPlan p; memset(&p, 0, sizeof(p));
+  p.rc = MI355_EUNSUPPORTED;
+  if (!x || !y || !d) { p.rc = MI355_EINVAL; return p; }
+  p.fuse = d->moments_out ? 1 : (d->gn_bwd ? 2 : 0);
+  const bool fusable = stats_fusable(x, y, d);
+  long long b = 0;
+  if (d->wformat == MI355_W_OIDHW4) {
+    p.route = FWD_C4;
+    if (fusable && mi355_conv3d_c4_ok(x, d)) b = (long long)ceil_div(y->d, 4) * ceil_div(y->h, 8) * ceil_div(y->w, 8);
+  } else if (d->wformat == MI355_W_PACKED_F32_NARROW || (d->wformat == MI355_W_PACKED && d->precision == MI355_PREC_F32 && mi355_conv3d_narrow_ok(x, y, d))) {
+    p.route = FWD_NARROW;
+  } else if (d->wformat != MI355_W_PACKED) {
+    p.rc = MI355_EINVAL;
+  } else if (mi355_conv3d_uses_bf16(d)) {
+    p.route = FWD_LP16;
+    if (fusable) p.stats_blocks = mi355_conv3d_bf16_stats_blocks(x, y, d);
+  } else if (d->in_mode == MI355_IN_ZERO_INSERT && (d->stride != 1 || d->kd != 3 || d->pad != 1)) {
+    p.rc = MI355_EINVAL;
+  } else if (mi355_conv3d_s2c32_ok(x, y, d)) {
+    p.route = FWD_S2C32;
+    if (fusable) p.stats_blocks = mi355_conv3d_s2c32_stats_blocks(y);
+  } else if (mi355_conv3d_s2c32_dgrad_ok(x, y, d)) {
+    p.route = FWD_S2C32_DGRAD;
+  } else if (mi355_conv3d_k1_stream_ok(x, y, d)) {
+    p.route = FWD_K1_STREAM;
+  } else if (x->dtype == y->dtype) {      // one storage type per call here (the first-layer kernels above take fp32 x with either y)
+    p.route = FWD_MFMA;
+    p.cfg = select_cfg(d->kd, d->stride, (long long)d->out_d * d->out_h * d->out_w * x->n,
+                       (d->kd == 1 && d->out_mode == MI355_OUT_D2S) ? 8 * y->c : y->c, d->in_mode);
+    const MfmaCfg& c = kMfmaCfg[p.cfg];
+    // two-level accumulation: always for >= 4 channel chunks; for the 1-tile-per-wave configurations (16 accumulator
+    // registers, deep layers) already from 2 chunks, where it is free
+    // (not for the 4-tile configuration: 64 more live registers would cost a wave of occupancy per SIMD)
+    const int cinP = (x->c + 7) / 8 * 8, cinL = d->in_mode == MI355_IN_S2D ? 8 * x->c : x->c;
+    p.tl = d->kd == 3 && c.tiles <= 2 && (cinP >= 4 * c.kc || (c.tiles == 1 && cinP >= 2 * c.kc));
+    p.fullj = (cinL + 7) / 8 * 8 % c.kc == 0;
+    // only the 3x3x3 kernels reading a plain / normalised input carry the fused-statistics epilogue
+    if (fusable && d->kd == 3 && (d->in_mode == MI355_IN_PLAIN || d->in_mode == MI355_IN_AFFINE_ACT))
+      b = (long long)ceil_div(y->d, c.tz) * ceil_div(y->h, c.ty) * ceil_div(y->w, c.tx);
+  }
+  if (b > 0 && b <= 0x7fffffffLL) p.stats_blocks = (int32_t)b;
+  return p;
+}
+
 // the forms that exist for 16-bit activation storage: what a UNet3D with activation_storage="bf16" sends here (the 3x3x3 stride-1
 // convolutions of that network run on the 16-bit-operand kernels of conv3d_bf16*.hip): 1x1x1 on a plain input, 3x3x3 stride 2 on a plain
 // input (with or without the moments epilogue), and the zero-insert form (stride-2 dgrad, ConvTranspose3d(k3, s2))
@@ -693,7 +798,7 @@ template <typename TA> constexpr bool act_form_exists(int kd, int stride, int im
 }
 
 template <int KD, int STRIDE, int TZ, int TY, int TX, int KC, int PADV, int WM, int WN, int MT, int NT, typename TA = float>
-static int launch_cfg(ConvArgs& a, int in_mode, void* stream) {
+static int launch_cfg(ConvArgs& a, int in_mode, const FwdPlan& p, void* stream) {
   constexpr int HZ = (TZ - 1) * STRIDE + KD, HY = (TY - 1) * STRIDE + KD, HX = (TX - 1) * STRIDE + KD;
   constexpr size_t lds = (size_t)HZ * HY * HX * (KC + PADV) * sizeof(float);
   static_assert(lds <= 64 * 1024, "LDS tile must fit the default 64 KiB dynamic window");
@@ -701,13 +806,8 @@ static int launch_cfg(ConvArgs& a, int in_mode, void* stream) {
   a.coTiles = ceil_div(a.Cout, 32 * WN * NT);
   const long long blocks = (long long)a.N * a.tilesZ * a.tilesY * a.tilesX * a.coTiles;
   if (blocks <= 0 || blocks > 0x7fffffffLL) return MI355_EINVAL;
-  // two-level accumulation: always for >= 4 channel chunks; for the 1-tile-per-wave configurations (16 accumulator
-  // registers, deep layers) already from 2 chunks, where it is free
-  // (not for the 4-tile configuration: 64 more live registers would cost a wave of occupancy per SIMD)
-  const bool tl = KD == 3 && MT * NT <= 2 && (a.CinP >= 4 * KC || (MT * NT == 1 && a.CinP >= 2 * KC));
-  const bool fullj = a.CinP % KC == 0;
-  if (a.g.mom && a.g.gnb) return MI355_EUNSUPPORTED;     // a call is a forward (moments) or a dgrad (norm-backward sums), not both
-  const int fuse = a.g.mom ? 1 : (a.g.gnb ? 2 : 0);
+  const bool tl = p.tl, fullj = p.fullj;
+  const int fuse = p.fuse;
   if (fuse && (KD != 3 || (in_mode != MI355_IN_PLAIN && in_mode != MI355_IN_AFFINE_ACT))) return MI355_EUNSUPPORTED;
 #define MI355_LAUNCH_CONV4(SS, IM, LDSB, FU)                                                                                         \
   do {                                                                                                                         \
@@ -747,86 +847,35 @@ static int launch_cfg(ConvArgs& a, int in_mode, void* stream) {
   return LAUNCH_CHECK();
 }
 
-// Configuration table (ids are stable; see mi355_conv3d_fwd_config):
-//  0/1: 1x1x1, 256-voxel flat tiles, 64/32 output channels per workgroup
-//  2/3: 3x3x3 stride 2 (also the zero-insert form with stride template 1), 4x4x8 tiles, KC=8
-//  4/5: 3x3x3 stride 1, 4x8x8 tiles, KC=16 (large volumes: >= 131072 output voxels in the batch)
-//  6/7: 3x3x3 stride 1, 2x4x8 / 4x4x8 tiles, KC=32 (small volumes, so the grid still covers 256 CUs)
-//  8:   3x3x3 stride 1, 4x4x8 tiles x 64 output channels, KC=16, 2 M tiles per wave (32768 .. 131071 output voxels, > 32 output
-//       channels: each B fragment feeds two MFMA tiles; +10 % over configuration 6 on the 32^3-level layers)
-static int select_cfg(int kd, int stride, long long vox, int cout, int in_mode = MI355_IN_PLAIN) {
-  if (kd == 1) return cout > 32 ? 0 : 1;
-  if (stride == 2) return cout > 32 ? 2 : 3;
-  if (vox >= 256LL * 512 || in_mode == MI355_IN_ZERO_INSERT) return cout > 32 ? 4 : 5;   // zero-insert: parity-class tiles need 4x8x8
-  if (cout > 32 && vox >= 64LL * 512) return 8;
-  return cout > 32 ? 6 : 7;
-}
 
-// spatial tile (TZ, TY, TX) of each configuration id (select_cfg); 1x1x1 tiles are 256 voxels of the flattened volume
-static void cfg_tile(int cfg, int& tz, int& ty, int& tx) {
-  switch (cfg) {
-    case 0: case 1: tz = 1; ty = 1; tx = 256; break;
-    case 4: case 5: tz = 4; ty = 8; tx = 8; break;
-    case 6: tz = 2; ty = 4; tx = 8; break;
-    default: tz = 4; ty = 4; tx = 8; break;      // 2, 3, 7, 8
+// the instantiation of configuration p.cfg (kMfmaCfg) for storage type TA; 16-bit storage: the 1x1x1 and the stride-2 / zero-insert forms only
+// (with exact-fp32 3x3x3 stride-1 arithmetic: no such kernel, act_form_exists)
+template <typename TA>
+static int launch_mfma(ConvArgs& a, int im, const FwdPlan& p, void* stream) {
+  constexpr bool f32 = std::is_same<TA, float>::value;
+  switch (p.cfg) {
+    case 0: return launch_cfg<1, 1, 1, 1, 256, 32, 4, 4, 1, 2, 2, TA>(a, im, p, stream);
+    case 1: return launch_cfg<1, 1, 1, 1, 256, 32, 4, 4, 1, 2, 1, TA>(a, im, p, stream);
+    case 2: return launch_cfg<3, 2, 4, 4, 8, 8, 0, 4, 1, 1, 2, TA>(a, im, p, stream);
+    case 3: return launch_cfg<3, 2, 4, 4, 8, 8, 0, 4, 1, 1, 1, TA>(a, im, p, stream);
+    case 4: return launch_cfg<3, 1, 4, 8, 8, 16, 4, 4, 1, 2, 2, TA>(a, im, p, stream);
+    case 5: return launch_cfg<3, 1, 4, 8, 8, 16, 4, 4, 1, 2, 1, TA>(a, im, p, stream);
+    case 6: if constexpr (f32) return launch_cfg<3, 1, 2, 4, 8, 32, 4, 2, 2, 1, 1>(a, im, p, stream); break;
+    case 7: if constexpr (f32) return launch_cfg<3, 1, 4, 4, 8, 32, 4, 4, 1, 1, 1>(a, im, p, stream); break;
+    case 8: if constexpr (f32) return launch_cfg<3, 1, 4, 4, 8, 16, 4, 2, 2, 2, 1>(a, im, p, stream); break;
   }
-}
-
-// can this call fuse norm statistics into its epilogue? (plain, un-windowed output: what is stored IS the logical tensor)
-static bool stats_fusable(const mi355_act* x, const mi355_act* y, const mi355_conv_desc* d) {
-  if (!x || !y || !d || d->out_mode != MI355_OUT_PLAIN || d->in_mode == MI355_IN_S2D) return false;
-  if (d->off_z || d->off_y || d->off_x || d->out_d != y->d || d->out_h != y->h || d->out_w != y->w) return false;
-  if ((d->kd != 1 && d->kd != 3) || (d->stride != 1 && d->stride != 2)) return false;
-  return true;
-}
-
-int mi355_conv3d_fwd_bf16_impl(const mi355_act* x, const void* wp, const mi355_act* y, const mi355_conv_desc* d, void* stream);
-int mi355_conv3d_bf16_kernel_name(const mi355_act* x, const mi355_act* y, const mi355_conv_desc* d, char* out, size_t n);
-int32_t mi355_conv3d_bf16_stats_blocks(const mi355_act* x, const mi355_act* y, const mi355_conv_desc* d);
-int mi355_conv3d_c4_ok(const mi355_act* x, const mi355_conv_desc* d);
-int mi355_conv3d_c4_fwd_impl(const mi355_act* x, const float* w, const mi355_act* y, const mi355_conv_desc* d, void* stream);
-int mi355_conv3d_narrow_ok(const mi355_act* x, const mi355_act* y, const mi355_conv_desc* d);
-int mi355_conv3d_narrow_impl(const mi355_act* x, const float* wp, const mi355_act* y, const mi355_conv_desc* d, void* stream);
-// conv3d_s2.hip: the z-marching 32 -> 32 channel stride-2 forward
-int mi355_conv3d_s2c32_ok(const mi355_act* x, const mi355_act* y, const mi355_conv_desc* d);
-int32_t mi355_conv3d_s2c32_stats_blocks(const mi355_act* y);
-int mi355_conv3d_s2c32_fwd_impl(const mi355_act* x, const float* wp, const mi355_act* y, const mi355_conv_desc* d, void* stream);
-int mi355_conv3d_s2c32_dgrad_ok(const mi355_act* x, const mi355_act* y, const mi355_conv_desc* d);
-// conv3d_k1_stream.hip: 1x1x1 forward / data gradient of bf16 tensors as wave streams
-int mi355_conv3d_k1_stream_ok(const mi355_act* x, const mi355_act* y, const mi355_conv_desc* d);
-int mi355_conv3d_k1_stream_impl(const mi355_act* x, const float* wp, const mi355_act* y, const mi355_conv_desc* d, void* stream);
-int mi355_conv3d_s2c32_dgrad_impl(const mi355_act* x, const float* wp, const mi355_act* y, const mi355_conv_desc* d, void* stream);
-
-extern "C" int mi355_conv3d_uses_bf16(const mi355_conv_desc* d) {
-  return d && d->precision != MI355_PREC_F32 && d->kd == 3 && d->stride == 1 &&
-         (d->in_mode == MI355_IN_PLAIN || d->in_mode == MI355_IN_AFFINE_ACT);
+  return MI355_EUNSUPPORTED;
 }
 
 extern "C" int32_t mi355_conv3d_stats_blocks(const mi355_act* x, const mi355_act* y, const mi355_conv_desc* d) {
-  if (!stats_fusable(x, y, d)) return 0;
-  if (d->wformat == MI355_W_PACKED_F32_NARROW || (d->wformat == MI355_W_PACKED && d->precision == MI355_PREC_F32 && mi355_conv3d_narrow_ok(x, y, d)))
-    return 0;
-  long long b;
-  if (d->wformat == MI355_W_OIDHW4) {
-    if (!mi355_conv3d_c4_ok(x, d)) return 0;
-    b = (long long)ceil_div(y->d, 4) * ceil_div(y->h, 8) * ceil_div(y->w, 8);
-  } else if (mi355_conv3d_uses_bf16(d)) {
-    return mi355_conv3d_bf16_stats_blocks(x, y, d);
-  } else if (mi355_conv3d_s2c32_ok(x, y, d)) {
-    return mi355_conv3d_s2c32_stats_blocks(y);
-  } else if (d->kd == 1 || (d->in_mode != MI355_IN_PLAIN && d->in_mode != MI355_IN_AFFINE_ACT)) {
-    return 0;                 // only the 3x3x3 kernels reading a plain / normalised input carry the fused-statistics epilogue
-  } else {
-    int tz, ty, tx;
-    cfg_tile(select_cfg(d->kd, d->stride, (long long)y->d * y->h * y->w * x->n, y->c, d->in_mode), tz, ty, tx);
-    b = (long long)ceil_div(y->d, tz) * ceil_div(y->h, ty) * ceil_div(y->w, tx);
-  }
-  return b > 0 && b <= 0x7fffffffLL ? (int32_t)b : 0;
+  return plan_fwd(x, y, d).stats_blocks;
 }
 
-static int fill_gn_fuse(GnFuseArgs& g, const mi355_act* x, const mi355_act* y, const mi355_conv_desc* d) {
+// (also the 16-bit forward's, conv3d_bf16.hip)
+int mi355_fill_gn_fuse(GnFuseArgs& g, const mi355_act* x, const mi355_act* y, const mi355_conv_desc* d) {
   memset(&g, 0, sizeof(g));
   if (!d->moments_out && !d->gn_bwd) return 0;
+  if (d->moments_out && d->gn_bwd) return MI355_EUNSUPPORTED;      // a call is a forward (moments) or a dgrad (norm-backward sums), not both
   if (!stats_fusable(x, y, d)) return MI355_EUNSUPPORTED;
   g.mom = d->moments_out;
   if (d->gn_bwd) {
@@ -851,23 +900,20 @@ extern "C" int mi355_conv3d_fwd(const mi355_act* x, const float* wp, const mi355
   if (d->in_mode == MI355_IN_S2D && d->out_mode == MI355_OUT_D2S) return MI355_EUNSUPPORTED;
   if (d->out_mode != MI355_OUT_PLAIN && d->out_mode != MI355_OUT_D2S) return MI355_EINVAL;
   if (d->precision < MI355_PREC_F32 || d->precision > MI355_PREC_F16) return MI355_EINVAL;
-  if (d->wformat == MI355_W_OIDHW4) return mi355_conv3d_c4_fwd_impl(x, wp, y, d, stream);
-  const bool wants_stats = d->moments_out || d->gn_bwd;
-  if (d->wformat == MI355_W_PACKED_F32_NARROW) return wants_stats ? MI355_EUNSUPPORTED : mi355_conv3d_narrow_impl(x, wp, y, d, stream);
-  if (d->wformat != MI355_W_PACKED) return MI355_EINVAL;
-  if (d->precision == MI355_PREC_F32 && mi355_conv3d_narrow_ok(x, y, d))
-    return wants_stats ? MI355_EUNSUPPORTED : mi355_conv3d_narrow_impl(x, wp, y, d, stream);
-  if (mi355_conv3d_uses_bf16(d)) {
-    if (d->out_d <= 0 || d->out_h <= 0 || d->out_w <= 0) return MI355_EINVAL;
-    return mi355_conv3d_fwd_bf16_impl(x, wp, y, d, stream);
+  const FwdPlan p = plan_fwd(x, y, d);
+  switch (p.route) {
+    case FWD_REFUSED: return p.rc;
+    case FWD_C4: return mi355_conv3d_c4_fwd_impl(x, wp, y, d, stream);
+    case FWD_NARROW: return p.fuse ? MI355_EUNSUPPORTED : mi355_conv3d_narrow_impl(x, wp, y, d, stream);
+    case FWD_LP16:
+      if (d->out_d <= 0 || d->out_h <= 0 || d->out_w <= 0) return MI355_EINVAL;
+      return mi355_conv3d_fwd_bf16_impl(x, wp, y, d, stream);
+    case FWD_S2C32: return mi355_conv3d_s2c32_fwd_impl(x, wp, y, d, stream);
+    case FWD_S2C32_DGRAD: return mi355_conv3d_s2c32_dgrad_impl(x, wp, y, d, stream);
+    case FWD_K1_STREAM: return mi355_conv3d_k1_stream_impl(x, wp, y, d, stream);
+    case FWD_MFMA: break;
   }
-  if (d->in_mode == MI355_IN_ZERO_INSERT && (d->stride != 1 || d->kd != 3 || d->pad != 1)) return MI355_EINVAL;
-  if (mi355_conv3d_s2c32_ok(x, y, d)) return mi355_conv3d_s2c32_fwd_impl(x, wp, y, d, stream);
-  if (mi355_conv3d_s2c32_dgrad_ok(x, y, d)) return mi355_conv3d_s2c32_dgrad_impl(x, wp, y, d, stream);
-  if (mi355_conv3d_k1_stream_ok(x, y, d)) return mi355_conv3d_k1_stream_impl(x, wp, y, d, stream);
-  if (x->dtype != y->dtype) return MI355_EUNSUPPORTED;      // one storage type per call here (the first-layer kernels above take fp32 x with either y)
-  const bool lp = act_is_lp16(x->dtype);
-  if (lp && (y->c % 4 || y->ld % 4 || ((uintptr_t)y->p & 7))) return MI355_EINVAL;
+  if (act_is_lp16(x->dtype) && (y->c % 4 || y->ld % 4 || ((uintptr_t)y->p & 7))) return MI355_EINVAL;
   ConvArgs a;
   a.x = (const float*)x->p; a.xld = x->ld; a.wp = wp; a.y = (float*)y->p; a.yld = y->ld;
   a.res = (const float*)d->residual; a.resld = d->residual_ld;
@@ -879,16 +925,13 @@ extern "C" int mi355_conv3d_fwd(const mi355_act* x, const float* wp, const mi355
   a.pad = d->pad;
   a.in_slope = d->in_slope; a.outmode = d->out_mode; a.cD = a.cH = a.cW = 1; a.fC = 4;
   if (a.Do <= 0 || a.Ho <= 0 || a.Wo <= 0) return MI355_EINVAL;
-  { const int rcg = fill_gn_fuse(a.g, x, y, d); if (rcg) return rcg; }
+  { const int rcg = mi355_fill_gn_fuse(a.g, x, y, d); if (rcg) return rcg; }
   if (a.res && a.resld < a.Cout) return MI355_EINVAL;
   const int im = d->in_mode;
-  const int cfg = select_cfg(d->kd, d->stride, (long long)a.Do * a.Ho * a.Wo * a.N, a.Cout, im);
+  // 1x1x1: flatten (d,h,w) along x so tiles are 256 consecutive voxels (no halo); n stays separate for the per-(n,c) affine prologue.
+  ConvArgs f = a;
   if (d->kd == 1) {
     if (d->stride != 1 || im == MI355_IN_ZERO_INSERT) return MI355_EUNSUPPORTED;
-    const int cfg1 = select_cfg(1, 1, 0, d->out_mode == MI355_OUT_D2S ? 8 * y->c : y->c);
-    // 1x1x1: flatten (d,h,w) along x so tiles are 256 consecutive voxels (no halo); n stays separate for the
-    // per-(n,c) affine prologue.
-    ConvArgs f = a;
     long long vin = (long long)a.Di * a.Hi * a.Wi, vout = (long long)a.Do * a.Ho * a.Wo;
     long long vy = (long long)a.yD * a.yH * a.yW;
     if (im == MI355_IN_S2D) {
@@ -905,67 +948,28 @@ extern "C" int mi355_conv3d_fwd(const mi355_act* x, const float* wp, const mi355
     }
     if (vin != vout || vy != vout || a.offz || a.offy || a.offx || vin > 0x7fffffffLL) return MI355_EUNSUPPORTED;
     f.Di = f.Hi = 1; f.Wi = (int)vin; f.Do = f.Ho = 1; f.Wo = (int)vout; f.yD = f.yH = 1; f.yW = (int)vy; f.pad = 0;
-    if (lp) {
-      int rc1 = MI355_EUNSUPPORTED;
-      ACT_TYPED_LP16(x->dtype, T16, rc1 = cfg1 == 0 ? (launch_cfg<1, 1, 1, 1, 256, 32, 4, 4, 1, 2, 2, T16>(f, im, stream))
-                                                     : (launch_cfg<1, 1, 1, 1, 256, 32, 4, 4, 1, 2, 1, T16>(f, im, stream)));
-      return rc1;
-    }
-    if (cfg1 == 0) return launch_cfg<1, 1, 1, 1, 256, 32, 4, 4, 1, 2, 2>(f, im, stream);
-    return launch_cfg<1, 1, 1, 1, 256, 32, 4, 4, 1, 2, 1>(f, im, stream);
   }
-  if (lp) {
-    int rcl = MI355_EUNSUPPORTED;      // (16-bit storage with exact-fp32 3x3x3 stride-1 arithmetic: no such kernel, act_form_exists)
-    ACT_TYPED_LP16(x->dtype, T16,
-      switch (cfg) {
-        case 2: rcl = (launch_cfg<3, 2, 4, 4, 8, 8, 0, 4, 1, 1, 2, T16>(a, im, stream)); break;
-        case 3: rcl = (launch_cfg<3, 2, 4, 4, 8, 8, 0, 4, 1, 1, 1, T16>(a, im, stream)); break;
-        case 4: rcl = (launch_cfg<3, 1, 4, 8, 8, 16, 4, 4, 1, 2, 2, T16>(a, im, stream)); break;
-        case 5: rcl = (launch_cfg<3, 1, 4, 8, 8, 16, 4, 4, 1, 2, 1, T16>(a, im, stream)); break;
-        default: break;
-      });
-    return rcl;
-  }
-  switch (cfg) {
-    case 2: return launch_cfg<3, 2, 4, 4, 8, 8, 0, 4, 1, 1, 2>(a, im, stream);
-    case 3: return launch_cfg<3, 2, 4, 4, 8, 8, 0, 4, 1, 1, 1>(a, im, stream);
-    case 4: return launch_cfg<3, 1, 4, 8, 8, 16, 4, 4, 1, 2, 2>(a, im, stream);
-    case 5: return launch_cfg<3, 1, 4, 8, 8, 16, 4, 4, 1, 2, 1>(a, im, stream);
-    case 6: return launch_cfg<3, 1, 2, 4, 8, 32, 4, 2, 2, 1, 1>(a, im, stream);
-    case 8: return launch_cfg<3, 1, 4, 4, 8, 16, 4, 2, 2, 2, 1>(a, im, stream);
-    default: return launch_cfg<3, 1, 4, 4, 8, 32, 4, 4, 1, 1, 1>(a, im, stream);
-  }
+  int rc;
+  ACT_TYPED(x->dtype, TA, rc = launch_mfma<TA>(f, im, p, stream));
+  return rc;
 }
 
 // Name of the kernel instantiation mi355_conv3d_fwd launches for this problem, as it appears (demangled) in a
 // rocprofv3 kernel trace -- lets bench.py attribute HIP-event timings to the same symbol the profile reports.
 extern "C" int mi355_conv3d_fwd_config(const mi355_act* x, const mi355_act* y, const mi355_conv_desc* d, char* out, size_t n) {
   if (!x || !y || !d || !out || n < 8) return MI355_EINVAL;
-  if (d->wformat == MI355_W_PACKED_F32_NARROW || (d->wformat == MI355_W_PACKED && d->precision == MI355_PREC_F32 && mi355_conv3d_narrow_ok(x, y, d))) {
-    snprintf(out, n, "conv3d_c4_dgrad");
-    return 0;
+  const FwdPlan p = plan_fwd(x, y, d);
+  switch (p.route) {
+    case FWD_REFUSED: return p.rc;
+    case FWD_C4: snprintf(out, n, d->precision == MI355_PREC_F32 ? "conv3d_c4_fwd" : "conv3d_c4_fwd_bf16"); return 0;
+    case FWD_NARROW: snprintf(out, n, "conv3d_c4_dgrad"); return 0;
+    case FWD_LP16: return mi355_conv3d_bf16_kernel_name(x, y, d, out, n);
+    case FWD_S2C32: snprintf(out, n, "conv3d_s2c32_fwd"); return 0;
+    case FWD_S2C32_DGRAD: snprintf(out, n, "conv3d_s2c32_dgrad"); return 0;
+    case FWD_K1_STREAM: snprintf(out, n, "conv3d_k1_stream_bf16"); return 0;
+    case FWD_MFMA: break;
   }
-  if (d->wformat == MI355_W_PACKED && mi355_conv3d_uses_bf16(d)) return mi355_conv3d_bf16_kernel_name(x, y, d, out, n);
-  if (mi355_conv3d_s2c32_ok(x, y, d)) { snprintf(out, n, "conv3d_s2c32_fwd"); return 0; }
-  if (mi355_conv3d_s2c32_dgrad_ok(x, y, d)) { snprintf(out, n, "conv3d_s2c32_dgrad"); return 0; }
-  if (mi355_conv3d_k1_stream_ok(x, y, d)) { snprintf(out, n, "conv3d_k1_stream_bf16"); return 0; }
-  const int cfg = select_cfg(d->kd, d->stride, (long long)d->out_d * d->out_h * d->out_w * x->n,
-                             (d->kd == 1 && d->out_mode == MI355_OUT_D2S) ? 8 * y->c : y->c, d->in_mode);
-  const int stride_t = d->in_mode == MI355_IN_ZERO_INSERT ? 1 : d->stride;
-  static const char* const tags[9] = {"1, 1, 1, 1, 256, 32, 4, 4, 1, 2, 2", "1, 1, 1, 1, 256, 32, 4, 4, 1, 2, 1",
-                                      "4, 4, 8, 8, 0, 4, 1, 1, 2", "4, 4, 8, 8, 0, 4, 1, 1, 1",
-                                      "3, 1, 4, 8, 8, 16, 4, 4, 1, 2, 2", "3, 1, 4, 8, 8, 16, 4, 4, 1, 2, 1",
-                                      "3, 1, 2, 4, 8, 32, 4, 2, 2, 1, 1", "3, 1, 4, 4, 8, 32, 4, 4, 1, 1, 1",
-                                      "3, 1, 4, 4, 8, 16, 4, 2, 2, 2, 1"};
-  static const int kcs[9] = {32, 32, 8, 8, 16, 16, 32, 32, 16};
-  const int cinP = (x->c + 7) / 8 * 8;
-  const bool one = cfg == 3 || cfg == 6 || cfg == 7;     // MT * NT == 1
-  const bool four = cfg == 2 || cfg == 4;                 // MT * NT == 4 (cfg 2: NT = 2, MT = 1 -> 2 tiles, allowed)
-  const char* tl = (d->kd == 3 && cfg != 4 && (cinP >= 4 * kcs[cfg] || (one && cinP >= 2 * kcs[cfg]))) ? "true" : "false";
-  (void)four;
-  const int cinL = d->in_mode == MI355_IN_S2D ? 8 * x->c : x->c;
-  const char* fj = (((cinL + 7) / 8 * 8) % kcs[cfg] == 0) ? "true" : "false";
-  if (cfg == 2 || cfg == 3) snprintf(out, n, "conv3d_mfma<3, %d, %s, %d, %s, %s>", stride_t, tags[cfg], d->in_mode, tl, fj);
-  else snprintf(out, n, "conv3d_mfma<%s, %d, %s, %s>", tags[cfg], d->in_mode, tl, fj);
+  snprintf(out, n, "conv3d_mfma<%d, %d, %s, %d, %s, %s>", d->kd, d->stride, kMfmaCfg[p.cfg].args, d->in_mode, p.tl ? "true" : "false",
+           p.fullj ? "true" : "false");
   return 0;
 }

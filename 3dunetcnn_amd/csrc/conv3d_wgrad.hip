@@ -456,10 +456,6 @@ int mi355_conv3d_wgrad_k1_lp_ok(const mi355_act* x, const mi355_act* dy, const m
 size_t mi355_conv3d_wgrad_k1_lp_workspace(const mi355_act* x, const mi355_act* dy, const mi355_conv_desc* d);
 int mi355_conv3d_wgrad_k1_lp_impl(const mi355_act* x, const mi355_act* dy, float* dw, const mi355_conv_desc* d, void* ws, size_t ws_bytes,
                                   void* stream);
-static int wgrad_uses_bf16(const mi355_conv_desc* d) {
-  return d->precision != MI355_PREC_F32 && d->kd == 3 && d->stride == 1 && d->pad == 1 && d->out_mode == MI355_OUT_PLAIN &&
-         (d->in_mode == MI355_IN_PLAIN || d->in_mode == MI355_IN_AFFINE_ACT);
-}
 
 struct WgradPlan { int tz, ty, tx, ntiles, tilesZ, tilesY, tilesX, splits, ciTiles, coTiles, wv, coutL; size_t ws_bytes; int ok; };
 
@@ -524,17 +520,45 @@ static RingPlan plan_wgrad_ring(const mi355_act* x, const mi355_act* dy) {
   p.ok = 1;
   return p;
 }
-static int wgrad_uses_ring(const mi355_conv_desc* d) { return d->kd == 3 && d->stride == 1 && d->pad == 1 && d->out_mode == MI355_OUT_PLAIN; }
+
+// ---- routing: mi355_conv3d_wgrad launches the route, mi355_conv3d_wgrad_workspace and mi355_conv3d_wgrad_config read it ----
+enum WgradRoute { WG_REFUSED, WG_C4, WG_LP_TR, WG_K1_LP, WG_LP16, WG_S2C32, WG_RING, WG_MFMA };
+static WgradRoute route_wgrad(const mi355_act* x, const mi355_act* dy, const mi355_conv_desc* d) {
+  if (!x || !dy || !d) return WG_REFUSED;
+  if (mi355_conv3d_c4_ok(x, d)) return WG_C4;
+  if (mi355_conv3d_wgrad_lp_tr_ok(x, dy, d)) return WG_LP_TR;
+  if (mi355_conv3d_wgrad_k1_lp_ok(x, dy, d)) return WG_K1_LP;
+  const bool k3s1 = d->kd == 3 && d->stride == 1 && d->pad == 1 && d->out_mode == MI355_OUT_PLAIN;
+  if (k3s1 && d->precision != MI355_PREC_F32 && (d->in_mode == MI355_IN_PLAIN || d->in_mode == MI355_IN_AFFINE_ACT)) return WG_LP16;
+  if (x->dtype != dy->dtype) return WG_REFUSED;       // (the first-layer kernel above takes fp32 x with either dy)
+  if (mi355_conv3d_s2c32_wgrad_ok(x, dy, d)) return WG_S2C32;
+  // the plane ring; exact-fp32 3x3x3 arithmetic on 16-bit tensors: no kernel (and no caller)
+  if (k3s1) return x->dtype == MI355_ACT_F32 ? WG_RING : WG_REFUSED;
+  return WG_MFMA;
+}
 
 extern "C" size_t mi355_conv3d_wgrad_workspace(const mi355_act* x, const mi355_act* dy, const mi355_conv_desc* d) {
-  if (mi355_conv3d_c4_ok(x, d)) return mi355_conv3d_c4_wgrad_workspace(x, dy, d);
-  if (mi355_conv3d_wgrad_lp_tr_ok(x, dy, d)) return mi355_conv3d_wgrad_lp_tr_workspace(x, dy, d);
-  if (mi355_conv3d_wgrad_k1_lp_ok(x, dy, d)) return mi355_conv3d_wgrad_k1_lp_workspace(x, dy, d);
-  if (d && wgrad_uses_bf16(d)) return mi355_conv3d_wgrad_bf16_workspace(x, dy, d);
-  if (x && dy && d && wgrad_uses_ring(d)) { RingPlan r = plan_wgrad_ring(x, dy); return r.ok ? r.ws_bytes : 0; }
-  if (mi355_conv3d_s2c32_wgrad_ok(x, dy, d)) return mi355_conv3d_s2c32_wgrad_workspace(dy);
-  WgradPlan p = plan_wgrad(x, dy, d);
-  return p.ok ? p.ws_bytes : 0;
+  switch (route_wgrad(x, dy, d)) {
+    case WG_C4: return mi355_conv3d_c4_wgrad_workspace(x, dy, d);
+    case WG_LP_TR: return mi355_conv3d_wgrad_lp_tr_workspace(x, dy, d);
+    case WG_K1_LP: return mi355_conv3d_wgrad_k1_lp_workspace(x, dy, d);
+    case WG_LP16: return mi355_conv3d_wgrad_bf16_workspace(x, dy, d);
+    case WG_S2C32: return mi355_conv3d_s2c32_wgrad_workspace(dy);
+    case WG_RING: { const RingPlan r = plan_wgrad_ring(x, dy); return r.ok ? r.ws_bytes : 0; }
+    case WG_MFMA: { const WgradPlan p = plan_wgrad(x, dy, d); return p.ok ? p.ws_bytes : 0; }
+    default: return 0;
+  }
+}
+
+// Name of the kernel mi355_conv3d_wgrad launches for this problem (the reduction that follows it is not named)
+extern "C" int mi355_conv3d_wgrad_config(const mi355_act* x, const mi355_act* dy, const mi355_conv_desc* d, char* out, size_t n) {
+  static const char* const kernels[] = {nullptr, "conv3d_c4_wgrad", "conv3d_wgrad_lp_tr", "conv3d_wgrad_k1_stream", "conv3d_wgrad_k3_bf16",
+                                        "conv3d_s2c32_wgrad", "conv3d_wgrad_ring", "conv3d_wgrad_mfma<%d, %d>"};      // by WgradRoute
+  if (!out || n < 8) return MI355_EINVAL;
+  const WgradRoute route = route_wgrad(x, dy, d);
+  if (route == WG_REFUSED) return MI355_EUNSUPPORTED;
+  snprintf(out, n, kernels[route], d->kd, d->stride);
+  return 0;
 }
 
 template <int KD, int STRIDE, int TZ, int TY, int TX, typename TA>
@@ -559,22 +583,25 @@ extern "C" int mi355_conv3d_wgrad(const mi355_act* x, const mi355_act* dy, float
   if (d->in_mode == MI355_IN_AFFINE_ACT && (!d->in_scale || !d->in_shift)) return MI355_EINVAL;
   if (d->in_mode == MI355_IN_AFFINE_ACT && !(d->act_slope >= 0.f && d->act_slope <= 1.f)) return MI355_EINVAL;
   if (d->precision < MI355_PREC_F32 || d->precision > MI355_PREC_F16) return MI355_EINVAL;
-  if (mi355_conv3d_c4_ok(x, d)) return mi355_conv3d_c4_wgrad_impl(x, dy, dw, d, ws, ws_bytes, stream);
-  if (mi355_conv3d_wgrad_lp_tr_ok(x, dy, d)) return mi355_conv3d_wgrad_lp_tr_impl(x, dy, dw, d, ws, ws_bytes, stream);
-  if (mi355_conv3d_wgrad_k1_lp_ok(x, dy, d)) return mi355_conv3d_wgrad_k1_lp_impl(x, dy, dw, d, ws, ws_bytes, stream);
-  if (wgrad_uses_bf16(d)) return mi355_conv3d_wgrad_bf16_impl(x, dy, dw, d, ws, ws_bytes, stream);
-  if (x->dtype != dy->dtype) return MI355_EUNSUPPORTED;       // (the first-layer kernel above takes fp32 x with either dy)
-  if (mi355_conv3d_s2c32_wgrad_ok(x, dy, d)) return mi355_conv3d_s2c32_wgrad_impl(x, dy, dw, d, ws, ws_bytes, stream);
-  if (wgrad_uses_ring(d)) {
-    if (x->dtype != MI355_ACT_F32) return MI355_EUNSUPPORTED;   // exact-fp32 3x3x3 arithmetic on 16-bit tensors: no kernel (and no caller)
+  const WgradRoute route = route_wgrad(x, dy, d);
+  switch (route) {
+    case WG_REFUSED: return MI355_EUNSUPPORTED;
+    case WG_C4: return mi355_conv3d_c4_wgrad_impl(x, dy, dw, d, ws, ws_bytes, stream);
+    case WG_LP_TR: return mi355_conv3d_wgrad_lp_tr_impl(x, dy, dw, d, ws, ws_bytes, stream);
+    case WG_K1_LP: return mi355_conv3d_wgrad_k1_lp_impl(x, dy, dw, d, ws, ws_bytes, stream);
+    case WG_LP16: return mi355_conv3d_wgrad_bf16_impl(x, dy, dw, d, ws, ws_bytes, stream);
+    case WG_S2C32: return mi355_conv3d_s2c32_wgrad_impl(x, dy, dw, d, ws, ws_bytes, stream);
+    case WG_RING: case WG_MFMA: break;
+  }
+  WgradArgs a; memset(&a, 0, sizeof(a));
+  a.x = (const float*)x->p; a.xld = x->ld; a.dy = (const float*)dy->p; a.dyld = dy->ld; a.ws = (float*)ws;
+  a.in_scale = d->in_scale; a.in_shift = d->in_shift; a.slope = d->act_slope; a.in_slope = d->in_slope;
+  a.N = x->n; a.Di = x->d; a.Hi = x->h; a.Wi = x->w; a.Cin = x->c;
+  a.Do = dy->d; a.Ho = dy->h; a.Wo = dy->w; a.Cout = dy->c;
+  if (route == WG_RING) {
     RingPlan r = plan_wgrad_ring(x, dy);
     if (!r.ok) return MI355_EUNSUPPORTED;
     if (ws_bytes < r.ws_bytes) return MI355_EWORKSPACE;
-    WgradArgs a; memset(&a, 0, sizeof(a));
-    a.x = (const float*)x->p; a.xld = x->ld; a.dy = (const float*)dy->p; a.dyld = dy->ld; a.ws = (float*)ws;
-    a.in_scale = d->in_scale; a.in_shift = d->in_shift; a.slope = d->act_slope; a.in_slope = d->in_slope;
-    a.N = x->n; a.Di = x->d; a.Hi = x->h; a.Wi = x->w; a.Cin = x->c;
-    a.Do = dy->d; a.Ho = dy->h; a.Wo = dy->w; a.Cout = dy->c;
     a.tilesZ = r.zchunks; a.pad = r.planes;          // ring kernel: z chunks per column / planes per chunk
     a.tilesY = r.tilesY; a.tilesX = r.tilesX; a.splits = r.splits; a.ntiles = r.chunks; a.ciTiles = r.ciTiles; a.coTiles = r.coTiles;
     dim3 grid(r.splits, r.ciTiles, r.coTiles);
@@ -592,15 +619,9 @@ extern "C" int mi355_conv3d_wgrad(const mi355_act* x, const mi355_act* dy, float
   WgradPlan p = plan_wgrad(x, dy, d);
   if (!p.ok) return MI355_EUNSUPPORTED;
   if (ws_bytes < p.ws_bytes) return MI355_EWORKSPACE;
-  WgradArgs a;
-  a.x = (const float*)x->p; a.xld = x->ld; a.dy = (const float*)dy->p; a.dyld = dy->ld; a.ws = (float*)ws;
-  a.in_scale = d->in_scale; a.in_shift = d->in_shift; a.slope = d->act_slope;
-  a.N = x->n; a.Di = x->d; a.Hi = x->h; a.Wi = x->w; a.Cin = x->c;
-  a.Do = dy->d; a.Ho = dy->h; a.Wo = dy->w; a.Cout = dy->c; a.pad = d->pad;
-  a.tilesZ = p.tilesZ; a.tilesY = p.tilesY; a.tilesX = p.tilesX; a.ntiles = p.ntiles;
+  a.pad = d->pad; a.tilesZ = p.tilesZ; a.tilesY = p.tilesY; a.tilesX = p.tilesX; a.ntiles = p.ntiles;
   a.splits = p.splits; a.ciTiles = p.ciTiles; a.coTiles = p.coTiles;
-  a.in_slope = d->in_slope; a.dymode = d->out_mode; a.cD = x->d; a.cH = x->h; a.cW = x->w; a.fC = dy->c;
-  a.Cout = p.coutL;
+  a.dymode = d->out_mode; a.cD = x->d; a.cH = x->h; a.cW = x->w; a.fC = dy->c; a.Cout = p.coutL;
   int rc;
   if (d->kd == 1) {
     const long long vi = (long long)x->d * x->h * x->w;

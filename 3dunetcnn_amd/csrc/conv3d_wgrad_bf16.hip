@@ -437,21 +437,11 @@ __global__ __launch_bounds__(576 + 64 * NLW) MIN_WAVES_PER_SIMD((NS == 1 && MT =
   }
 }
 
-static int nsplit_of_w(int precision) {
-  switch (precision) {
-    case MI355_PREC_BF16X3: return 2;
-    case MI355_PREC_BF16X6: return 3;
-    case MI355_PREC_BF16: return 1;
-    case MI355_PREC_F16: return 1;
-    default: return 0;
-  }
-}
-
 struct WBPlan { int tilesY, tilesX, ntiles, splits, ciTiles, coTiles32, coTilesWG, mt; size_t ws_bytes; int ok; };
 
 static WBPlan plan_wb(const mi355_act* x, const mi355_act* dy, const mi355_conv_desc* d) {
   WBPlan p; memset(&p, 0, sizeof(p));
-  if (!x || !dy || !d || !nsplit_of_w(d->precision)) return p;
+  if (!x || !dy || !d || !lp_nsplit(d->precision)) return p;
   if (d->kd != 3 || d->stride != 1 || d->pad != 1) return p;
   if (x->dtype != dy->dtype || !act_matches_precision(x->dtype, d->precision)) return p;      // 16-bit storage goes with operands of its own type
   if (x->d != dy->d || x->h != dy->h || x->w != dy->w) return p;
@@ -460,8 +450,9 @@ static WBPlan plan_wb(const mi355_act* x, const mi355_act* dy, const mi355_conv_
   if (nt <= 0 || nt > 0x7fffffffLL) return p;
   p.ntiles = (int)nt;
   p.ciTiles = ceil_div(x->c, 32); p.coTiles32 = ceil_div(dy->c, 32);
-  p.mt = (dy->c > 32 && nsplit_of_w(d->precision) < 3) ? 2 : 1;     // 3 planes x 64 co would not fit the 160 KiB LDS
-  { const char* e = getenv("MI355_WGRAD_LP_MT"); if (e && atoi(e) == 1) p.mt = 1; }      // A/B switch (tools/r5_prep_ab.sh): 32-channel workgroups everywhere
+  p.mt = (dy->c > 32 && lp_nsplit(d->precision) < 3) ? 2 : 1;     // 3 planes x 64 co would not fit the 160 KiB LDS
+  static const bool mt1 = [] { const char* e = getenv("MI355_WGRAD_LP_MT"); return e && atoi(e) == 1; }();      // read once per process
+  if (mt1) p.mt = 1;      // A/B switch (tools/r5_prep_ab.sh): 32-channel workgroups everywhere
   p.coTilesWG = ceil_div(p.coTiles32, p.mt);
   const int wgs = p.ciTiles * p.coTilesWG;
   int splits = ceil_div(512, wgs);
@@ -508,7 +499,7 @@ int mi355_conv3d_wgrad_bf16_impl(const mi355_act* x, const mi355_act* dy, float*
   a.N = x->n; a.D = x->d; a.H = x->h; a.W = x->w; a.Cin = x->c; a.Cout = dy->c;
   a.tilesY = p.tilesY; a.tilesX = p.tilesX; a.ntiles = p.ntiles;
   a.splits = p.splits; a.ciTiles = p.ciTiles; a.coTiles32 = p.coTiles32;
-  const int ns = nsplit_of_w(d->precision);
+  const int ns = lp_nsplit(d->precision);
   int rc;
   if (x->dtype == MI355_ACT_BF16) rc = p.mt == 2 ? launch_wb<1, 2, false, bf16_t>(a, p, d->in_mode, stream) : launch_wb<1, 1, false, bf16_t>(a, p, d->in_mode, stream);
   else if (x->dtype == MI355_ACT_F16) rc = p.mt == 2 ? launch_wb<1, 2, true, f16_t>(a, p, d->in_mode, stream) : launch_wb<1, 1, true, f16_t>(a, p, d->in_mode, stream);

@@ -332,7 +332,8 @@ static WTPlan plan_wt(const mi355_act* x, const mi355_act* dy, const mi355_conv_
   if (cols * p.zchunks * pairs > 0x3fffffffLL) return p;
   p.ncol = (int)(cols * p.zchunks);
   p.colsPer = 1;      // (2 for more than 1024 workgroups was measured: 512 -> 256 @16^3 x4 0.259 -> 0.338 ms -- short columns want the parallelism)
-  { const char* e = getenv("MI355_WGRAD_LP_COLS"); if (e && atoi(e) > 0) p.colsPer = atoi(e); }
+  static const int cols_env = [] { const char* e = getenv("MI355_WGRAD_LP_COLS"); return e ? atoi(e) : 0; }();      // read once per process
+  if (cols_env > 0) p.colsPer = cols_env;
   p.nslab = ceil_div(p.ncol, p.colsPer);
   p.ws_bytes = (size_t)pairs * p.nslab * 27 * 1024 * sizeof(float);
   p.ok = 1;

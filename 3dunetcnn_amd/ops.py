@@ -22,6 +22,16 @@ from ._lib import (IN_AFFINE_ACT, IN_PLAIN, IN_S2D, IN_ZERO_INSERT, OUT_D2S, OUT
 # views rebuilt every time) -- the A/B switch of the host-enqueue measurement (tools/host_enqueue.py, profiles/r5_host_enqueue.txt)
 HOST_CACHES = os.environ.get("MI355_HOST_CACHES", "1") != "0"
 
+# Profiler families (Backend.prof names; bench.py's roofline rows and PMC_FAMILY key on them) of the kernels mi355_conv3d_fwd_config /
+# mi355_conv3d_wgrad_config name, by name prefix; any other kernel is a family of its own. A weight-gradient family adds " (+reduce)".
+PROF_FAMILIES = (("conv3d_k3_bf16<", "conv3d_k3_bf16<...>"), ("conv3d_k3_lp_zring", "conv3d_k3_bf16<...>"), ("conv3d_c4_fwd", "conv3d_c4_fwd"),
+                 ("conv3d_wgrad_k3_bf16", "conv3d_wgrad_k3_bf16<...>"))
+
+
+def prof_family(kernel):
+    return next((family for prefix, family in PROF_FAMILIES if kernel.startswith(prefix)), kernel)
+
+
 ACT_DTYPES = {torch.float32: _lib.ACT_F32, torch.bfloat16: _lib.ACT_BF16, torch.float16: _lib.ACT_F16}      # storage types of an activation view
 
 
@@ -170,6 +180,7 @@ class Backend:
         if self.device.type == "cuda":
             self._dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
         self._wino_ok = {}          # call signature -> mi355_conv3d_wino_supported's answer (conv_fwd)
+        self._c4_bwd_ok = {}        # call signature -> mi355_conv3d_c4_bwd_supported's answer (c4_bwd_supported)
         self._ws_by_stream = {}     # launch stream handle -> workspace tensor: kernels of different streams must not share scratch
         self.precision = PREC_F32   # arithmetic of the 3x3x3 stride-1 convs: see set_precision()
         self.act_dtype = torch.float32   # storage type of the activations empty_act() makes (engine.HipNetBase sets it per network)
@@ -406,16 +417,14 @@ class Backend:
         # profiling: HIP events on the launch stream around this one kernel, keyed by the kernel's trace name
         name = ctypes.create_string_buffer(96)
         self.lib.mi355_conv3d_fwd_config(ctypes.byref(xd), ctypes.byref(yd), ctypes.byref(d), name, 96)
+        kernel = name.value.decode()
+        family = prof_family(kernel)
         variant = None
-        if d.wformat == W_OIDHW4:
-            name.value = b"conv3d_c4_fwd"
-        elif d.wformat == W_PACKED and self.lib.mi355_conv3d_uses_bf16(ctypes.byref(d)):
-            # one family, several kernels: the tile forms and (16-bit single-product modes, eligible shapes) the plane-ring form;
-            # mi355_conv3d_fwd_config names the instantiation this call launches exactly as a rocprofv3 trace prints it
-            variant = name.value.decode()
+        if family.endswith("<...>"):
+            # one family, several kernels: the row keeps the instantiation this call launches, named exactly as a rocprofv3 trace prints it
+            variant = kernel
             if os.environ.get("MI355_PROF_SHAPES") == "1":      # developer aid: one row per layer shape (tools/r6_call.sh)
                 variant += f" [{x.c}->{y.c} @{out_dhw[0]} x{x.shape[0]}]"
-            name.value = b"conv3d_k3_bf16<...>"
         nvox = x.shape[0] * out_dhw[0] * out_dhw[1] * out_dhw[2]
         flops = 2.0 * nvox * x.c * y.c * kd ** 3 * (8 if (in_mode == IN_S2D or out_mode == OUT_D2S) else 1)
         if in_mode == IN_ZERO_INSERT:
@@ -427,7 +436,7 @@ class Backend:
         check(self.lib.mi355_conv3d_fwd(ctypes.byref(xd), wptr, ctypes.byref(yd), ctypes.byref(d), self.stream()), "conv3d_fwd")
         e1.record()
         fused = float(yb) * nvox * y.c * ((residual is not None) + (gparts is not None))
-        self._prof_add(name.value.decode(), flops, byts, e0, e1, variant, fused)
+        self._prof_add(family, flops, byts, e0, e1, variant, fused)
         return self._fold_after(y, gparts)
 
     # -- Winograd form of the 3x3x3 stride-1 conv (csrc/conv3d_wino.hip) -------------------------------------------------------------
@@ -539,28 +548,23 @@ class Backend:
             flops = 2.0 * nvox * x.c * dy.c * kd ** 3
             byts = (x.buf.element_size() * (x.shape[0] * x.shape[1] * x.shape[2] * x.shape[3] * x.c) + dy.buf.element_size() * nvox * dy.c +
                     4.0 * kd ** 3 * x.c * dy.c)
-            bf = self.precision != PREC_F32 and kd == 3 and stride == 1 and pad == 1 and in_mode in (IN_PLAIN, IN_AFFINE_ACT) and out_mode == OUT_PLAIN
-            c4 = x.c == 4 and kd == 3 and stride == 1 and pad == 1 and in_mode in (IN_PLAIN, IN_AFFINE_ACT) and out_mode == OUT_PLAIN
-            s2 = (kd == 3 and stride == 2 and pad == 1 and x.c == 32 and dy.c == 32 and in_mode == IN_PLAIN and out_mode == OUT_PLAIN
-                  and os.environ.get("MI355_S2_KERNEL", "1") != "0")
-            tr = (bf and x.buf.element_size() == 2 and x.c % 32 == 0 and dy.c % 32 == 0 and x.shape[2] >= 8 and x.shape[3] >= 16
-                  and os.environ.get("MI355_WGRAD_LP_TR", "1") != "0")      # (plan_wt in csrc/conv3d_wgrad_lp.hip decides; this is the label)
-            k1 = (kd == 1 and stride == 1 and in_mode == IN_PLAIN and out_mode == OUT_PLAIN and x.buf.dtype == dy.buf.dtype
-                  and (x.c // 32, dy.c // 32) in ((1, 2), (2, 1), (2, 4), (4, 2)) and x.c % 32 == 0 and dy.c % 32 == 0
-                  and os.environ.get("MI355_WGRAD_K1_STREAM", "1") != "0")  # (plan_wk1 in csrc/conv3d_wgrad_lp.hip decides; this is the label)
-            self._prof_add("conv3d_wgrad_k1_stream (+reduce)" if k1 else "conv3d_c4_wgrad (+reduce)" if c4 else "conv3d_s2c32_wgrad (+reduce)" if s2 else "conv3d_wgrad_lp_tr (+reduce)" if tr
-                           else "conv3d_wgrad_k3_bf16<...> (+reduce)" if bf
-                           else "conv3d_wgrad_ring (+reduce)" if (kd == 3 and stride == 1 and pad == 1 and out_mode == OUT_PLAIN)
-                           else f"conv3d_wgrad_mfma<{kd}, {stride}> (+reduce)", flops, byts, e0, e1)
+            name = ctypes.create_string_buffer(96)
+            self.lib.mi355_conv3d_wgrad_config(ctypes.byref(xd), ctypes.byref(dyd), ctypes.byref(d), name, 96)
+            self._prof_add(prof_family(name.value.decode()) + " (+reduce)", flops, byts, e0, e1)
 
     # -- first-layer backward in one pass over dy (csrc/conv3d_c4_bwd.hip) -----------------------------------------------------------------
     def c4_bwd_supported(self, x, dy, in_mode=IN_AFFINE_ACT, slope=0.0, scale=None, shift=None, in_slope=None):
         """Can the fused first-layer backward take this pair (fp32 4-channel input, 32-channel dy of any storage type; its arithmetic is exact fp32 in every precision mode)? MI355_C4_BWD=0: never."""
         if os.environ.get("MI355_C4_BWD", "1") == "0" or x.c != 4 or dy.c != 32:
             return False
-        d = self._desc(3, 1, 1, in_mode, slope, scale, shift, None, None, None, (0, 0, 0), dy.shape[1:4], [], in_slope, OUT_PLAIN)
-        xd, dyd = x.desc(), dy.desc()
-        return bool(self.lib.mi355_conv3d_c4_bwd_supported(ctypes.byref(xd), ctypes.byref(dyd), ctypes.byref(d)))
+        # asked once per call signature, like _wino_ok (mi355_conv3d_c4_bwd checks the same conditions again on every call)
+        key = (x.shape, x.ld, x.dtype, x.ptr() & 15, dy.shape, dy.ld, dy.dtype, dy.ptr() & 15, in_mode, slope, scale is None, shift is None)
+        ok = self._c4_bwd_ok.get(key) if HOST_CACHES else None
+        if ok is None:
+            d = self._desc(3, 1, 1, in_mode, slope, scale, shift, None, None, None, (0, 0, 0), dy.shape[1:4], [], in_slope, OUT_PLAIN)
+            xd, dyd = x.desc(), dy.desc()
+            ok = self._c4_bwd_ok[key] = bool(self.lib.mi355_conv3d_c4_bwd_supported(ctypes.byref(xd), ctypes.byref(dyd), ctypes.byref(d)))
+        return ok
 
     def c4_bwd(self, x, dy, wp, dw, groups, gamma, mean_rstd, scale, shift, dgamma, dbeta, slope=0.0, in_slope=None):
         """Backward of [GroupNorm(4 channels) -> act -> Conv3d(4 -> 32, k3)] whose input needs no gradient: dw (OIDHW) and dgamma / dbeta in

@@ -200,6 +200,9 @@ int mi355_conv3d_fwd_config(const mi355_act* x, const mi355_act* y, const mi355_
 size_t mi355_conv3d_wgrad_workspace(const mi355_act* x, const mi355_act* dy, const mi355_conv_desc* desc);
 int mi355_conv3d_wgrad(const mi355_act* x, const mi355_act* dy, float* dw, const mi355_conv_desc* desc,
                        void* ws, size_t ws_bytes, void* stream);
+/* Writes the name of the weight-gradient kernel mi355_conv3d_wgrad launches for this problem (e.g. "conv3d_wgrad_ring",
+ * "conv3d_wgrad_mfma<1, 1>"; the counterpart of mi355_conv3d_fwd_config). MI355_EUNSUPPORTED: no kernel takes this call. */
+int mi355_conv3d_wgrad_config(const mi355_act* x, const mi355_act* dy, const mi355_conv_desc* desc, char* out, size_t n);
 
 /* ---- GroupNorm / InstanceNorm ----------------------------------------------------------------- */
 /* Statistics of torch.nn.GroupNorm(G, C, eps, affine) (myronenko.py:23-31) / InstanceNorm3d (G == C):

@@ -1,5 +1,7 @@
 // TEST INFRASTRUCTURE ONLY -- see emu.h.
 #include "emu.h"
+#include <mutex>
+#include <string>
 
 namespace emu {
 
@@ -43,4 +45,23 @@ void run_block(BlockState& bs) {
   }
 }
 
+static std::mutex g_launch_mu;
+static std::string g_launches;
+
+void record_launch(const char* kernel) {
+  std::lock_guard<std::mutex> lock(g_launch_mu);
+  g_launches += kernel;
+  g_launches += '\n';
+}
+
 }  // namespace emu
+
+// The kernel expressions LAUNCHed since the previous call, one per line (as written in the source: "(conv3d_mfma<KD, ...>)"), into
+// out[0, n); returns the length of the full record and clears it. (Not an mi355_ symbol: the library's C ABI is unaffected.)
+extern "C" size_t emu_take_launches(char* out, size_t n) {
+  std::lock_guard<std::mutex> lock(emu::g_launch_mu);
+  const size_t len = emu::g_launches.size();
+  if (out && n) snprintf(out, n, "%s", emu::g_launches.c_str());
+  emu::g_launches.clear();
+  return len;
+}

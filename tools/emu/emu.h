@@ -120,8 +120,13 @@ void fiber_entry();
 
 void run_block(BlockState& bs);
 
+// the kernel expression of every LAUNCH, in order (read and cleared by emu_take_launches in emu.cpp): tests check that a config query
+// names the kernel the entry point launches
+void record_launch(const char* kernel);
+
 template <class F>
-void launch(emu_dim3 grid, emu_dim3 block, size_t lds_bytes, F body) {
+void launch(emu_dim3 grid, emu_dim3 block, size_t lds_bytes, F body, const char* kernel = nullptr) {
+  if (kernel) record_launch(kernel);
   // MI355_EMU_NOEXEC=1: a launch returns at once (tools/host_enqueue.py times the host side of a step -- Python, ctypes, the C dispatch --
   // at the real shapes without a GPU; outputs are garbage, nothing may check them)
   static const bool noexec = [] { const char* v = getenv("MI355_EMU_NOEXEC"); return v && v[0] == '1'; }();
@@ -310,7 +315,7 @@ static inline double atomicAdd(double* p, double v) {
 static inline unsigned atomicAdd(unsigned* p, unsigned v) { return __atomic_fetch_add(p, v, __ATOMIC_RELAXED); }
 
 #define LAUNCH(kernel, grid, block, lds, stream, ...) \
-  emu::launch((grid), (block), (lds), [=]() { kernel(__VA_ARGS__); })
+  emu::launch((grid), (block), (lds), [=]() { kernel(__VA_ARGS__); }, #kernel)
 #define LAUNCH_CHECK() 0
 #define SET_MAX_DYN_LDS(kernel, bytes) do {} while (0)
 #define SCHED_BARRIER() do {} while (0)
