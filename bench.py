@@ -10,10 +10,17 @@ BASELINE.json configs[1] = UNet3D 4ch -> 3cls (default widths, 23 970 216 params
 Weak scaling: every rank processes its own batch; the only exchange is the bucketed RCCL gradient all-reduce
 overlapped with backward (3dunetcnn_amd/ddp.py). value = world * batch * K / max-over-ranks elapsed.
 
-Extra objects on the JSON line (tier contract):
-  roofline     -- dominant kernel (by summed HIP-event time inside the timed region): algorithmic FLOPs / time vs the
+A plain run does only what the headline figure needs: set up, warm up, time the K steps, write --dump-outputs if asked, print
+the JSON line. Everything below takes runs of its own and is measured only with --full (null or absent in a plain run;
+the --no-* flags switch single parts of a --full run off):
+  per_rank_host_enqueue_ms_per_step -- host time to enqueue one step onto an idle device (2 extra steps).
+  roofline     -- dominant kernel (by summed HIP-event time over serialized extra steps): algorithmic FLOPs / time vs the
                   fp32 MFMA peak (157.3 TFLOP/s, MI355X_MICROARCH.md), since the 3x3x3 convs are compute-bound in fp32
                   (SURVEY.md 7.3 #1); `hbm_gbps` gives the same launches' algorithmic bytes / time for reference.
+                  `first_layer` comes from the same events. With MI355_SIDE_STREAM=0 the events are those of the timed
+                  region itself, and a plain run reports both as well.
+  precision_modes -- the same step in the opt-in conv arithmetic modes (N=1, c2, fp32 only).
+  c3           -- BASELINE configs[2]'s per-GPU shape, measured by a child `bench.py --config c3 --full` (N=1, c2 only).
   cpu_baseline -- the oracle (CPU restatement of the reference graph, oracle/unet3d_ref.py) timed on this host for the
                   training step at N=1 on the full 128^3 patch: 1 warm-up + 3 timed steps (rank 0, N=1 runs only; ~40 s).
 """
@@ -75,13 +82,17 @@ def parse():
                     help="the step as ONE replayed HIP graph (3dunetcnn_amd/graph.py): forward + loss + backward captured; with N > 1 the "
                          "gradients are exchanged in one all-reduce of the flat buffer after the replay instead of per bucket from inside "
                          "backward. ~600 host launches per step become 3 (many ranks on one host, short steps)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need, each on runs of its own after the timed region: host "
+                         "enqueue time, the roofline pass, precision_modes, c3 and cpu_baseline (off by default: a plain run only sets up, "
+                         "warms up, times the steps, dumps if asked and prints the line)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
     ap.add_argument("--no-kernel-events", action="store_true", help="disable the per-launch HIP events (roofline -> null)")
     ap.add_argument("--no-c3", action="store_true",
-                    help="skip the short run of BASELINE configs[2]'s per-GPU shape (bf16 mixed, batch 4, 16-bit activation storage) that the "
-                         "default N=1 line carries under `c3` (a child process: python bench.py --config c3 --steps 20 --warmup 5)")
+                    help="with --full: skip the short run of BASELINE configs[2]'s per-GPU shape (bf16 mixed, batch 4, 16-bit activation "
+                         "storage) that the N=1 line carries under `c3` (a child process: python bench.py --config c3 --steps 20 --warmup 5 --full)")
     ap.add_argument("--no-precision-modes", action="store_true",
-                    help="skip the short extra runs of the opt-in conv arithmetic modes (reported under precision_modes, N=1 only)")
+                    help="with --full: skip the short extra runs of the opt-in conv arithmetic modes (reported under precision_modes, N=1 only)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the LAST timed step computed (rank 0) as DIR/<name>.npy, float32: loss, logits, "
                          "and the flat parameters / gradients after the optimizer step (c5: the inferred volume). Arrays above "
@@ -121,6 +132,16 @@ def _free_port():
     port = s.getsockname()[1]
     s.close()
     return port
+
+
+def host_threads(world):
+    """Threads of a rank's host-side torch ops: the CPUs the job may use -- OMP_NUM_THREADS when set, else the CPUs this process may run
+    on -- shared among the node's `world` ranks. os.cpu_count() counts the whole machine: on a box that grants a job a fraction of it, a
+    pool of that size oversubscribes the granted cores, and the set-up's host work (the synthetic batch) takes seconds instead of
+    a fraction of one, waiting on threads that are not running."""
+    env = os.environ.get("OMP_NUM_THREADS", "")
+    budget = int(env) if env.isdigit() and int(env) > 0 else len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    return max(1, budget // max(world, 1))
 
 
 def self_launch(n):
@@ -289,12 +310,13 @@ C3_KEYS = ("volumes_per_s_per_gpu", "ms_per_step", "workload", "activation_stora
 def c3_block(steps=20, warmup=5, timeout=600):
     """BASELINE configs[2] per GPU (the same model in bf16 mixed precision, batch 4 per GPU, 16-bit activation storage: the configuration
     the 8-GPU DDP run is quoted on, reference: AutocastUNet, segmentation/unet.py:53-58) measured by a CHILD process on this GPU after the
-    headline's timed region: `python bench.py --config c3 --steps 20 --warmup 5 --no-cpu-baseline` (5 + 2 steps were measured 16 % slow: the
-    first steps of a fresh process run before the allocator and the clocks have settled, profiles/r5_c3_warmup.txt). A separate process because the step
-    allocates the batch-4 activations of another network; its own line is what `--config c3` prints, this block keeps the figures a
-    reader of the driver's line needs. Informational: never `value`."""
+    headline's timed region: `python bench.py --config c3 --steps 20 --warmup 5 --no-cpu-baseline --full` (5 + 2 steps were measured 16 % slow:
+    the first steps of a fresh process run before the allocator and the clocks have settled, profiles/r5_c3_warmup.txt). A separate process because
+    the step allocates the batch-4 activations of another network; its own line is what `--config c3 --full` prints (--full for its roofline and
+    host enqueue time), this block keeps the figures a reader of the driver's line needs. Informational: never `value`."""
     import subprocess
-    cmd = [sys.executable, os.path.abspath(__file__), "--config", "c3", "--steps", str(steps), "--warmup", str(warmup), "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.abspath(__file__), "--config", "c3", "--steps", str(steps), "--warmup", str(warmup), "--no-cpu-baseline",
+           "--full"]
     try:
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, env=dict(os.environ, RANK="0", LOCAL_RANK="0", WORLD_SIZE="1"))
         line = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -310,7 +332,7 @@ def c3_block(steps=20, warmup=5, timeout=600):
             "mfma_pipe_frac": roof.get("mfma_pipe_frac"), "hbm_frac": roof.get("hbm_frac"),
             "traffic_over_algorithmic": roof.get("traffic_over_algorithmic"), "share_of_step": roof.get("share_of_step"),
             "per_rank_host_enqueue_ms_per_step": c.get("per_rank_host_enqueue_ms_per_step"),
-            "command": "python bench.py --config c3 --steps %d --warmup %d --no-cpu-baseline (child process, same GPU, after the timed region)" % (steps, warmup)}
+            "command": "python bench.py --config c3 --steps %d --warmup %d --no-cpu-baseline --full (child process, same GPU, after the timed region)" % (steps, warmup)}
 
 
 def bench_c5(args, unet, inferer_mod, dev):
@@ -355,7 +377,7 @@ def main():
     if world != args.gpus and rank == 0:
         print(f"bench.py: --gpus {args.gpus} but the launcher started {world} ranks; reporting n_gpus={world}", file=sys.stderr)
     emu = args.emulator_plumbing_test
-    torch.set_num_threads(max(1, (os.cpu_count() or 1) // max(world, 1)))      # host-side torch ops: no oversubscription across ranks
+    torch.set_num_threads(host_threads(world))                   # host-side torch ops: no oversubscription across ranks
     import torch.distributed as dist
     if emu:
         dev = torch.device("cpu")
@@ -481,7 +503,7 @@ def main():
     barrier()
     # Per-launch HIP events go into the timed region only when its launches are serialized (MI355_SIDE_STREAM=0: the rocprofv3 command
     # of profiles/): with the weight gradients on a second stream (the default) a launch's duration is not its own, the roofline is
-    # measured on extra steps after the timed region (below), and ~1200 event records per step inside the timed region are pure
+    # measured on extra steps after the timed region (below, --full only), and ~1200 event records per step inside the timed region are pure
     # perturbation (bf16, batch 4: 57.6 -> 75.0 ms/step with them).
     side = bool(getattr(model, "backward_side_stream", False)) and dev.type == "cuda"
     if not args.no_kernel_events and not side:
@@ -507,15 +529,17 @@ def main():
         dump_outputs(args.dump_outputs, dumped)
         del dumped
     last_logits.clear()
-    # Host enqueue time of one step, measured OUTSIDE the timed region on an idle device: inside it a GPU-bound loop runs the host into
-    # the launch queue's depth limit, and the time spent blocked there says nothing about the Python / launch work of a step.
-    host_s[0], host_s[1] = 0.0, 0
-    for _ in range(2):
-        step()
-        if dev.type == "cuda":
-            torch.cuda.synchronize()
-    host_ms = host_s[0] / max(host_s[1], 1) * 1e3
-    # Roofline pass. The timed region runs the weight-gradient kernels on a second stream (engine.py: backward_side_stream), where a
+    # Host enqueue time of one step (--full), measured OUTSIDE the timed region on an idle device: inside it a GPU-bound loop runs the host
+    # into the launch queue's depth limit, and the time spent blocked there says nothing about the Python / launch work of a step.
+    host_ms = None
+    if args.full:
+        host_s[0], host_s[1] = 0.0, 0
+        for _ in range(2):
+            step()
+            if dev.type == "cuda":
+                torch.cuda.synchronize()
+        host_ms = host_s[0] / max(host_s[1], 1) * 1e3
+    # Roofline pass (--full). The timed region runs the weight-gradient kernels on a second stream (engine.py: backward_side_stream), where a
     # launch shares the chip with the dgrad chain and its HIP-event duration is not its own. The kernel's rate is therefore measured
     # on ROOF_STEPS extra steps right after the timed region with that overlap switched off (one stream, every launch alone);
     # `value` / `ms_per_step` never include these steps. MI355_SIDE_STREAM=0 makes the timed region itself serialized (that is the
@@ -523,7 +547,7 @@ def main():
     prof = prof_timed
     roof_note = "HIP events over the timed region"
     ROOF_STEPS = 3
-    if not args.no_kernel_events and side:
+    if args.full and not args.no_kernel_events and side:
         model.backward_side_stream = False
         step()
         barrier()
@@ -541,7 +565,7 @@ def main():
 
     per_rank, per_rank_host = [dt], [host_ms]
     if world > 1:
-        mine = torch.tensor([dt, host_ms], dtype=torch.float64, device=dev)
+        mine = torch.tensor([dt, float("nan") if host_ms is None else host_ms], dtype=torch.float64, device=dev)
         every = [torch.zeros_like(mine) for _ in range(world)]
         dist.all_gather(every, mine)
         per_rank = [float(t[0].item()) for t in every]
@@ -664,7 +688,7 @@ def main():
                "per_rank_ms_per_step": [round(t / args.steps * 1e3, 3) for t in per_rank],
                # host time a rank spends enqueueing one step onto an idle device (Python + ~600 C-ABI launches in the eager form, 3 launches
                # with --graph; two extra steps after the timed region); the step is GPU-bound while this stays below ms_per_step
-               "per_rank_host_enqueue_ms_per_step": [round(t, 3) for t in per_rank_host],
+               "per_rank_host_enqueue_ms_per_step": None if host_ms is None else [round(t, 3) for t in per_rank_host],
                "communicator": {"backend": comm_backend, "world_size": comm_world, "rank_devices": rank_devices},
                "step_form": ("hip-graph replay + one flat all-reduce" + (" (uncaptured: emulator plumbing test)" if emu else "")) if graphed is not None
                             else "eager launches, bucketed all-reduce inside backward",
@@ -677,7 +701,7 @@ def main():
                                                 "weights, weight gradients and the loss fp32)" if args.storage != "fp32" else "fp32",
                           "global_batch": world * B, "parallelism": f"dp{world}"},
                "final_loss": round(loss_val, 6), "roofline": roofline, "first_layer": first_layer}
-        if world == 1 and args.precision == "fp32" and not args.no_precision_modes and args.config == "c2":
+        if args.full and world == 1 and args.precision == "fp32" and not args.no_precision_modes and args.config == "c2":
             # informational: the same step with the opt-in arithmetic modes of the 3x3x3 stride-1 convs;
             # `value` above is the exact-fp32 number
             modes = {}
@@ -708,9 +732,9 @@ def main():
                                                                "conv_arithmetic": ARITH[pm]}
             be.set_precision("fp32")
             out["precision_modes"] = modes
-        if world == 1 and args.precision == "fp32" and args.config == "c2" and args.model == "unet3d" and not args.no_c3 and not emu:
+        if args.full and world == 1 and args.precision == "fp32" and args.config == "c2" and args.model == "unet3d" and not args.no_c3 and not emu:
             out["c3"] = c3_block()
-        if world == 1 and not args.no_cpu_baseline and args.config == "c2":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.config == "c2":
             out["cpu_baseline"] = cpu_baseline(S, args.model)
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -29,6 +29,26 @@ def test_flag_defaults(monkeypatch):
     assert (a.gpus, a.steps, a.warmup) == (8, 7, 2)
 
 
+def test_full_is_off_by_default(monkeypatch):
+    b = _bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "7", "--warmup", "2"])
+    assert b.parse().full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "7", "--warmup", "2", "--full"])
+    a = b.parse()
+    assert a.full is True and (a.steps, a.warmup) == (7, 2)
+
+
+def test_host_threads_share_the_granted_cpus(monkeypatch):
+    """The host thread pool is sized from the CPUs the job may use (OMP_NUM_THREADS, else the process's CPU affinity), not from the
+    machine's count, and shared among the node's ranks."""
+    b = _bench()
+    monkeypatch.setenv("OMP_NUM_THREADS", "16")
+    assert (b.host_threads(1), b.host_threads(2), b.host_threads(32)) == (16, 8, 1)
+    monkeypatch.delenv("OMP_NUM_THREADS")
+    granted = len(os.sched_getaffinity(0))
+    assert b.host_threads(1) == granted and b.host_threads(granted + 1) == 1
+
+
 def test_cpu_baseline_leg_reports_the_contract_fields():
     r = _bench().cpu_baseline(32)          # the full 32^3 step (1 warm-up + 3 timed): a second of CPU work
     assert {"value", "unit", "cores", "kind", "sample"} <= set(r)          # the contract fields ...
@@ -260,8 +280,9 @@ def test_two_ranks_in_the_c3_and_the_graphed_form(emu_backend, extra, form, dtyp
 
 
 def test_c3_block_keeps_the_figures_of_the_child_line(monkeypatch):
-    """The default N = 1 line carries BASELINE configs[2]'s per-GPU shape under `c3` (verdict round 4, item 5): a child `bench.py --config c3`
-    whose line is reduced to the keys below; a failing child yields an `error` entry instead of taking the headline line down."""
+    """The N = 1 --full line carries BASELINE configs[2]'s per-GPU shape under `c3` (verdict round 4, item 5): a child
+    `bench.py --config c3 --full` (its roofline and host enqueue time are --full figures) whose line is reduced to the keys below; a failing
+    child yields an `error` entry instead of taking the headline line down."""
     b = _bench()
     child = {"value": 84.0, "ms_per_step": 47.6, "steps": 5, "warmup": 2, "dtype": "bf16 (mixed)", "per_rank_host_enqueue_ms_per_step": [9.0],
              "config": {"workload": "BASELINE configs[2]: ...", "activation_storage": "bf16 (...)"},
@@ -280,6 +301,7 @@ def test_c3_block_keeps_the_figures_of_the_child_line(monkeypatch):
     blk = b.c3_block()
     assert set(blk) == set(b.C3_KEYS) and blk["volumes_per_s_per_gpu"] == 84.0 and blk["mfma_pipe_frac"] == 0.3 and blk["hbm_frac"] == 0.12
     assert seen["cmd"][2:5] == ["--config", "c3", "--steps"] and "--no-cpu-baseline" in seen["cmd"]
+    assert "--full" in seen["cmd"] and "--full" in blk["command"]
     R.returncode = 3
     blk = b.c3_block()
     assert "error" in blk and "exited 3" in blk["error"]
@@ -311,6 +333,43 @@ def test_dump_outputs_writes_the_last_timed_step(emu_backend, tmp_path):
     for k in runs["a"]:
         assert np.array_equal(runs["a"][k], runs["b"][k]), k
     assert not np.array_equal(runs["a"]["parameters"], runs["c"]["parameters"])
+
+
+def test_plain_run_leaves_the_extra_steps_to_full(emu_backend, tmp_path):
+    """A plain run stops after the timed steps (and the dump); --full adds the host enqueue steps after them. Both runs time and dump the
+    same steps, so what they dump is identical (emulator plumbing run)."""
+    import numpy as np
+    env = dict(os.environ, RANK="0", LOCAL_RANK="0", WORLD_SIZE="1")
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--size", "8", "--batch", "1", "--steps", "2", "--warmup", "1",
+            "--emulator-plumbing-test"]
+    lines = {}
+    for tag, extra in (("plain", []), ("full", ["--full"])):
+        p = subprocess.run(base + extra + ["--dump-outputs", str(tmp_path / tag)], capture_output=True, text=True, env=env, timeout=900)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines[tag] = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][0])
+    plain, full = lines["plain"], lines["full"]
+    assert plain["per_rank_host_enqueue_ms_per_step"] is None and plain["roofline"] is None
+    assert len(full["per_rank_host_enqueue_ms_per_step"]) == 1 and full["per_rank_host_enqueue_ms_per_step"][0] > 0
+    for k in ("metric", "unit", "higher_is_better", "dtype", "steps", "warmup", "final_loss"):
+        assert plain[k] == full[k], k
+    for f in ("loss", "logits", "parameters", "gradients"):
+        assert np.array_equal(np.load(tmp_path / "plain" / (f + ".npy")), np.load(tmp_path / "full" / (f + ".npy"))), f
+
+
+@pytest.mark.gpu
+def test_plain_gpu_run_prints_the_headline_only():
+    """`bench.py` without --full on the GPU: the headline keys, none of the blocks that take runs of their own."""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "MI355_SIDE_STREAM")}
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--size", "64", "--batch", "1", "--steps", "2", "--warmup", "1"],
+                       capture_output=True, text=True, env=env, timeout=600)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, p.stdout
+    line = json.loads(lines[0])
+    assert line["metric"] == "training volumes/sec (64^3, 4ch->3cls)" and line["unit"] == "volumes/s" and line["higher_is_better"] is True
+    assert line["dtype"] == "f32" and line["ms_per_step"] > 0 and abs(line["value"] - 1e3 / line["ms_per_step"]) / line["value"] < 1e-3
+    assert line["roofline"] is None and line["first_layer"] is None and line["per_rank_host_enqueue_ms_per_step"] is None
+    assert not {"precision_modes", "c3", "cpu_baseline"} & set(line)
 
 
 def test_dump_sample_is_fixed_and_bounded():

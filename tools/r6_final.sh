@@ -14,8 +14,8 @@ cp gpurun_out/r6fbf16/hbm_traffic_pmc_bf16.csv profiles/r6_bf16_hbm_traffic_pmc.
 tools/trace_bf16.sh r6fc3 --config c3 > $out/trace_c3.log 2>&1
 cp gpurun_out/r6fc3/hbm_traffic_pmc_bf16.csv profiles/r6_c3_hbm_traffic_pmc.csv
 tools/gpu_profile.sh r6f bench
-timeout 600 python bench.py --config c3 > $out/bench_c3.json 2> $out/bench_c3.err; tail -c 300 $out/bench_c3.json
-timeout 600 python bench.py --precision bf16 --no-cpu-baseline > $out/bench_bf16.json 2> $out/bench_bf16.err
+timeout 600 python bench.py --config c3 --full > $out/bench_c3.json 2> $out/bench_c3.err; tail -c 300 $out/bench_c3.json
+timeout 600 python bench.py --precision bf16 --full --no-cpu-baseline > $out/bench_bf16.json 2> $out/bench_bf16.err
 {
 for a in "--config c4" "--config c5" "--model dynunet" "--graph" "--precision fp16" "--precision fp16 --storage fp32" "--size 64 --batch 1"; do
   echo -n "bench.py $a: "; timeout 600 python bench.py $a --no-cpu-baseline --no-precision-modes --no-kernel-events 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['metric'], '|', d['value'], d['unit'], '|', d['ms_per_step'], 'ms/step |', d.get('step_form', ''), '|', d['config'].get('activation_storage', '')[:12])"

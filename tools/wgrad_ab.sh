@@ -10,7 +10,7 @@ for c in "32 32 128" "64 32 128" "64 64 64" "128 128 32"; do
 done | tee $out/wgrad.txt
 for f in direct wino; do
   echo -n "step MI355_WGRAD_FORM=$f: "
-  MI355_WGRAD_FORM=$f python bench.py --no-cpu-baseline --no-precision-modes 2>/dev/null | python -c "
+  MI355_WGRAD_FORM=$f python bench.py --full --no-cpu-baseline --no-precision-modes 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); r=d['roofline']
 print(d['ms_per_step'], 'ms/step', d['value'], 'vol/s | dominant', r['kernel'], r['avg_launch_ms'], 'ms', r['achieved'], 'TF/s; ', {k:(round(v['s']*1e3/3,2), v['launches']//3) for k,v in r['all_kernels'].items()})"
