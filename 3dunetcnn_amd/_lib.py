@@ -102,6 +102,10 @@ SIGNATURES = {
     "mi355_zscore": (ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int64, c_void_p, c_size_t, c_void_p]),
     "mi355_resample_affine": (ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
                                              POINTER(ctypes.c_float), c_int32, c_int32, c_void_p]),
+    "mi355_augment_batch_workspace": (c_size_t, [c_int32, c_int32, c_int32, c_int32, c_int32]),
+    "mi355_augment_batch": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                           c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p,
+                                           c_size_t, c_void_p]),
     "mi355_wino_weight_elems": (c_size_t, [c_int32, c_int32]),
     "mi355_wino_pack_weight": (ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     "mi355_conv3d_wino_fwd": (ctypes.c_int, [POINTER(MiAct), c_void_p, POINTER(MiAct), POINTER(MiConvDesc), c_void_p]),

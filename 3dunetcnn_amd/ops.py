@@ -770,6 +770,33 @@ class Backend:
                                              out_shape[0], out_shape[1], out_shape[2], m, md, pd, self.stream()), "resample_affine")
         return dst
 
+    def augment_batch(self, image, label, matrices, gain=None, offset=None, out_shape=None, padding="border", normalize=False):
+        """Training augmentation of a batch in two launches (mi355_augment_batch). image [N, Ci, D, H, W] fp32; label None or
+        [N, Cl, D, H, W] uint8 / fp32; matrices [N, 3, 4] (or [N, 12]) fp32 ON THE DEVICE: output voxel -> source voxel, (z, y, x)
+        order; gain / offset None (1 / 0) or device fp32 [N, Ci]; out_shape None = the source extent. Returns (image', label')."""
+        assert image.is_contiguous() and image.dtype == torch.float32 and image.dim() == 5
+        n, ci = image.shape[:2]
+        out_shape = tuple(int(v) for v in (out_shape if out_shape is not None else image.shape[2:]))
+        assert matrices.dtype == torch.float32 and matrices.is_contiguous() and matrices.numel() == 12 * n and matrices.device == image.device
+        for t in (gain, offset):
+            assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n * ci and t.device == image.device)
+        out = torch.empty(n, ci, *out_shape, dtype=torch.float32, device=image.device)
+        lout, cl, ldt = None, 0, 0
+        if label is not None:
+            assert label.is_contiguous() and label.dim() == 5 and label.shape[0] == n and label.shape[2:] == image.shape[2:]
+            assert label.dtype in (torch.uint8, torch.float32) and label.device == image.device
+            cl, ldt = label.shape[1], 0 if label.dtype == torch.uint8 else 1
+            lout = torch.empty(n, cl, *out_shape, dtype=label.dtype, device=image.device)
+        ws, ws_bytes = None, 0
+        if normalize:
+            ws = self.ws(self.lib.mi355_augment_batch_workspace(n, ci, *out_shape))
+            ws_bytes = ws.numel() * 4
+        pd = {"border": 0, "zeros": 1}[padding]
+        check(self.lib.mi355_augment_batch(image.data_ptr(), out.data_ptr(), _p(label), _p(lout), ldt, n, ci, cl, image.shape[2], image.shape[3],
+                                           image.shape[4], out_shape[0], out_shape[1], out_shape[2], matrices.data_ptr(), _p(gain), _p(offset),
+                                           pd, int(bool(normalize)), _p(ws), ws_bytes, self.stream()), "augment_batch")
+        return out, lout
+
     # -- loss / optimizer ----------------------------------------------------------------------------------------
     def dice(self, logits, target, sigmoid=True, batch=False, squared_pred=False, smooth_nr=1e-5, smooth_dr=1e-5,
              want_grad=True, grad_scale=1.0, generalized=False, include_background=True):

@@ -10,6 +10,10 @@ dicts with device-resident tensors, so `.cuda()` in the loop is a no-op:
 
     loader = DeviceStager(loader, normalize=True, one_hot_labels=[[1, 2, 4], [1, 4], [4]])
 
+With `augment=HipAugmenter(...)` (augment.py) the staged batch also goes through the training augmentation on the copy stream: after
+the one-hot encode, and in place of the separate z-score -- the augmenter normalises between its spatial and its intensity
+transforms, where the reference does (datasets/segmentation.py:75-94).
+
 There is no CPU fallback: without an MI355X the constructor raises.
 """
 import torch
@@ -18,7 +22,7 @@ from . import ops as _ops
 
 
 class DeviceStager:
-    def __init__(self, loader, device=None, normalize=False, one_hot_labels=None, image_key="image", label_key="label", depth=2):
+    def __init__(self, loader, device=None, normalize=False, one_hot_labels=None, image_key="image", label_key="label", depth=2, augment=None):
         if not torch.cuda.is_available():
             raise RuntimeError("3dunetcnn_amd.staging needs an MI355X (no HIP device visible); there is no CPU fallback")
         self.loader = loader
@@ -28,7 +32,8 @@ class DeviceStager:
         self.depth = max(1, int(depth))
         self.copy_stream = torch.cuda.Stream(self.device)
         # its own Backend: the prologue kernels run on the copy stream and must not share the compute stream's workspace
-        self.be = _ops.Backend(device=self.device) if (normalize or one_hot_labels is not None) else None
+        self.be = _ops.Backend(device=self.device) if (normalize or one_hot_labels is not None or augment is not None) else None
+        self.augment = augment
 
     def __len__(self):
         return len(self.loader)
@@ -47,7 +52,7 @@ class DeviceStager:
                     out[k] = v.to(self.device, non_blocking=True)
                 else:
                     out[k] = v
-            if self.normalize and self.image_key in out:
+            if self.normalize and self.augment is None and self.image_key in out:
                 x = out[self.image_key].float().contiguous()
                 out[self.image_key] = torch.stack([self.be.zscore(x[n]) for n in range(x.shape[0])])
             if self.one_hot_labels is not None and self.label_key in out:
@@ -56,6 +61,14 @@ class DeviceStager:
                 if lm.dim() == 5:
                     lm = lm[:, 0]
                 out[self.label_key] = torch.stack([self.be.one_hot(lm[n].contiguous(), groups) for n in range(lm.shape[0])])
+            if self.augment is not None and self.image_key in out:
+                lab = out.get(self.label_key)
+                lab = lab if torch.is_tensor(lab) and lab.dim() == 5 else None
+                img, lab = self.augment(out[self.image_key].float().contiguous(), lab, normalize=self.normalize or self.augment.normalize,
+                                        _backend=self.be)
+                out[self.image_key] = img
+                if lab is not None:
+                    out[self.label_key] = lab
             ev = torch.cuda.Event()
             ev.record(self.copy_stream)
         return out, ev

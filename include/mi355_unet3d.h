@@ -329,6 +329,25 @@ int mi355_zscore(const float* x, float* y, int32_t c, int64_t voxels, void* ws, 
 #define MI355_RESAMPLE_NEAREST_FLOOR 2  /* floor (F.interpolate nearest) */
 int mi355_resample_affine(const float* src, float* dst, int32_t c, int32_t sd, int32_t sh, int32_t sw, int32_t dd, int32_t dh,
                           int32_t dw, const float* m, int32_t mode, int32_t padding, void* stream);
+/* Training augmentation of a whole batch in two launches (csrc/augment.hip; unet3d/datasets/segmentation.py:75-94: the MONAI spatial
+ * augmentations RandFlipD / RandRotateD / RandZoomD / RandSpatialCropD on image and label together, then NormalizeIntensityD, then
+ * RandScaleIntensityD / RandShiftIntensityD on the image). For sample s, with M_s = m + 12 * s in the convention of
+ * mi355_resample_affine (3x4 row-major, rows = source z, y, x of an output voxel) but in DEVICE memory, one map per sample:
+ *   1. img'[c][v] = trilinear(image[s][c], M_s * (v, 1)),  lbl'[k][v] = nearest(label[s][k], M_s * (v, 1))  (round half to even);
+ *      padding 0: border, 1: zeros outside, as mi355_resample_affine. A voxel whose source coordinates are integers is copied bit
+ *      for bit (signed axis permutations with integer translations: flips, crops, the identity).
+ *   2. normalize != 0: channel-wise z-score of img' with the semantics of mi355_zscore (population std, std 0 -> 1);
+ *   3. out[s][c][v] = z[c][v] * gain[s * ci + c] + offset[s * ci + c]   (gain / offset: device arrays, NULL = 1 / 0).
+ * image [n][ci][sd][sh][sw] fp32 -> out [n][ci][dd][dh][dw] fp32 (the output extent may differ: a crop); label (optional, with
+ * label_out) [n][cl][sd][sh][sw] -> [n][cl][dd][dh][dw], MI355_LABEL_U8 or MI355_LABEL_F32. The workspace (per-brick statistics
+ * records, folded in a fixed order: two calls give the same bits) is needed with normalize only. */
+#define MI355_LABEL_U8 0
+#define MI355_LABEL_F32 1
+size_t mi355_augment_batch_workspace(int32_t n, int32_t ci, int32_t dd, int32_t dh, int32_t dw);
+int mi355_augment_batch(const float* image, float* out, const void* label, void* label_out, int32_t label_dtype, int32_t n, int32_t ci,
+                        int32_t cl, int32_t sd, int32_t sh, int32_t sw, int32_t dd, int32_t dh, int32_t dw, const float* m,
+                        const float* gain, const float* offset, int32_t padding, int32_t normalize, void* ws, size_t ws_bytes,
+                        void* stream);
 
 /* ---- first-layer backward in one pass over dy (csrc/conv3d_c4_bwd.hip, round 6) ----------------------------------------------------------
  * The 4 -> 32 channel 3x3x3 conv of BASELINE.json's "128^3 x 4ch" line (unet3d/models/pytorch/classification/myronenko.py:17-21 via
