@@ -137,6 +137,11 @@ SIGNATURES = {
     "mi355_adam_step": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_double, c_double, c_double, c_double,
                                        c_double, c_int32, c_float, c_void_p]),
     "mi355_version": (c_char_p, []),
+    "mi355_ensemble_threshold": (ctypes.c_int, [c_void_p, c_int32, c_int64, c_float, c_void_p, c_void_p, c_void_p]),
+    "mi355_cc_workspace": (c_size_t, [c_int32, c_int32, c_int32, c_int32]),
+    "mi355_cc_label": (ctypes.c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "mi355_cc_filter": (ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int64, c_void_p, c_void_p,
+                                       c_void_p, c_size_t, c_void_p]),
 }
 
 

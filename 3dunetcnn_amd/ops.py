@@ -770,6 +770,38 @@ class Backend:
                                              out_shape[0], out_shape[1], out_shape[2], m, md, pd, self.stream()), "resample_affine")
         return dst
 
+    # -- after the network: ensemble mean, connected components, largest-component cleanup (csrc/components.hip) ---------------------
+    def ensemble_threshold(self, probs, threshold=0.5, want_mean=True, want_mask=True):
+        """probs [M, ...] fp32 (M stacked predictions of one sample). Returns (mean [...] fp32 or None, uint8 mask [...] or None);
+        mask = mean >= threshold (inclusive; postprocess() decodes with >)."""
+        assert probs.is_contiguous() and probs.dtype == torch.float32 and probs.dim() >= 2 and (want_mean or want_mask)
+        m, elems = probs.shape[0], probs[0].numel()
+        mean = torch.empty(probs.shape[1:], dtype=torch.float32, device=probs.device) if want_mean else None
+        mask = torch.empty(probs.shape[1:], dtype=torch.uint8, device=probs.device) if want_mask else None
+        check(self.lib.mi355_ensemble_threshold(probs.data_ptr(), m, elems, float(threshold), _p(mean), _p(mask), self.stream()),
+              "ensemble_threshold")
+        return mean, mask
+
+    def cc_label(self, mask, connectivity=6):
+        """mask [C, D, H, W] uint8 (nonzero = foreground), every channel on its own -> int32 labels [C, D, H, W]: 0 = background, else
+        1 + the smallest linear index (z*H + y)*W + x of the component. connectivity 6 | 26."""
+        assert mask.is_contiguous() and mask.dtype == torch.uint8 and mask.dim() == 4
+        labels = torch.empty(mask.shape, dtype=torch.int32, device=mask.device)
+        check(self.lib.mi355_cc_label(mask.data_ptr(), *mask.shape, int(connectivity), labels.data_ptr(), self.stream()), "cc_label")
+        return labels
+
+    def cc_filter(self, mask, labels, keep_largest=True, min_size=0):
+        """out = mask && size(component) >= min_size && (not keep_largest or the component is its channel's largest; ties -> the smaller
+        label). labels: cc_label(mask). Returns (uint8 [C, D, H, W], int32 stats [C, 3]: components, largest size, largest label)."""
+        assert mask.is_contiguous() and mask.dtype == torch.uint8 and mask.dim() == 4
+        assert labels.is_contiguous() and labels.dtype == torch.int32 and labels.shape == mask.shape and labels.device == mask.device
+        out = torch.empty_like(mask)
+        stats = torch.empty(mask.shape[0], 3, dtype=torch.int32, device=mask.device)
+        ws = self.ws(self.lib.mi355_cc_workspace(*mask.shape))
+        check(self.lib.mi355_cc_filter(mask.data_ptr(), labels.data_ptr(), *mask.shape, int(bool(keep_largest)), int(min_size), out.data_ptr(),
+                                       stats.data_ptr(), ws.data_ptr(), ws.numel() * 4, self.stream()), "cc_filter")
+        return out, stats
+
     def augment_batch(self, image, label, matrices, gain=None, offset=None, out_shape=None, padding="border", normalize=False):
         """Training augmentation of a batch in two launches (mi355_augment_batch). image [N, Ci, D, H, W] fp32; label None or
         [N, Cl, D, H, W] uint8 / fp32; matrices [N, 3, 4] (or [N, 12]) fp32 ON THE DEVICE: output voxel -> source voxel, (z, y, x)

@@ -10,6 +10,10 @@
   resample_to_match             MONAI ResampleToMatch(mode) of a prediction onto the source image grid,
                                 predict/volumetric.py:135-136, 168-170 (voxel map inv(A_src) @ A_dst; parity unpinned: MONAI absent)
 
+  ensemble_mean / connected_components / keep_largest_component / finish_prediction
+                                examples/sppin/process.py:258-274: np.mean over the cross-validation models' outputs, BinaryThreshold(0.5),
+                                ConnectedComponent, RelabelComponent(sortByObjectSize=True), == 1
+
 Inputs and outputs live on the GPU; there is no CPU fallback.
 """
 import torch
@@ -103,3 +107,73 @@ def resample_to_match(img, src_affine, dst_affine, dst_shape, mode="trilinear", 
     a_dst = torch.as_tensor(dst_affine, dtype=torch.float64).cpu()
     m = (torch.linalg.inv(a_src) @ a_dst)[:3, :].reshape(-1).tolist()
     return be.resample_affine(img.float().contiguous(), tuple(int(v) for v in dst_shape), m, mode, padding_mode)
+
+
+def _stacked(probabilities):
+    if isinstance(probabilities, (list, tuple)):
+        probabilities = torch.stack([p.float() for p in probabilities])
+    if probabilities.dim() != 5:
+        raise ValueError("probabilities: [M, C, D, H, W] or a list of [C, D, H, W]")
+    return probabilities.float().contiguous()
+
+
+def _connectivity(connectivity):
+    """scipy.ndimage.generate_binary_structure(3, k): 1 = faces (ITK fullyConnected=False), 3 = faces + edges + corners (True)."""
+    if connectivity == 2:
+        raise NotImplementedError("connectivity=2 (18 neighbours): only 1 (faces) and 3 (full)")
+    if connectivity not in (1, 3):
+        raise ValueError(f"connectivity {connectivity!r}: 1 or 3")
+    return 6 if connectivity == 1 else 26
+
+
+def _mask4(mask):
+    if mask.dim() not in (3, 4):
+        raise ValueError("mask: [D, H, W] or [C, D, H, W]")
+    m = mask if mask.dim() == 4 else mask[None]
+    if m.dtype != torch.uint8:
+        m = (m != 0).to(torch.uint8)
+    return m.contiguous()
+
+
+def ensemble_mean(probabilities, _backend=None):
+    """[M, C, D, H, W] or a list of M [C, D, H, W] -> their mean [C, D, H, W] (np.mean(np.stack(...), axis=0), process.py:258-262):
+    fp32 sum in index order, then a division by M."""
+    x = _stacked(probabilities)
+    return _be(x, _backend).ensemble_threshold(x, 0.5, want_mean=True, want_mask=False)[0]
+
+
+def connected_components(mask, connectivity=1, _backend=None):
+    """mask [D, H, W] or [C, D, H, W] (bool / uint8 / any: nonzero = foreground), every channel on its own -> (int32 labels of the same
+    shape, int64 number of components per channel [C], or a 0-dim tensor for a 3-D mask). A label is 0 for background, otherwise
+    1 + the smallest linear index (z*H + y)*W + x of its component: canonical, hence bitwise reproducible (ITK and scipy number
+    components 1, 2, ... in raster order of their first voxel: the same ORDER). connectivity as generate_binary_structure(3, k)."""
+    be, conn, m = _be(mask, _backend), _connectivity(connectivity), _mask4(mask)
+    labels = be.cc_label(m, conn)
+    v = m[0].numel()
+    count = (labels.reshape(m.shape[0], v) == torch.arange(1, v + 1, dtype=torch.int32, device=labels.device)).sum(dim=1)
+    return (labels, count) if mask.dim() == 4 else (labels[0], count[0])
+
+
+def keep_largest_component(mask, connectivity=1, min_size=0, _backend=None):
+    """The largest connected component of every channel (components smaller than min_size voxels never survive) -> uint8, same shape.
+    Ties in size go to the component met first in raster order -- this project's rule (what a stable size sort of raster-order labels,
+    and np.bincount(labels)[1:].argmax(), give; ITK itself is not installed here to compare against)."""
+    be, conn, m = _be(mask, _backend), _connectivity(connectivity), _mask4(mask)
+    out, _ = be.cc_filter(m, be.cc_label(m, conn), True, min_size)
+    return out if mask.dim() == 4 else out[0]
+
+
+def finish_prediction(probabilities, threshold=0.5, connectivity=1, keep_largest=True, min_size=0, _backend=None):
+    """examples/sppin/process.py:258-274 in one call: mean of the M models' probabilities, mask = mean >= threshold (inclusive, as
+    SimpleITK.BinaryThreshold's lower bound is -- activate_and_decode / convert_one_hot_to_label_map compare with >, as the
+    reference's decode does; both are kept), connected components (ConnectedComponent: faces = connectivity 1), and the largest one
+    per channel (RelabelComponent(sortByObjectSize=True) == 1) and / or those of at least min_size voxels.
+    Returns (mean probabilities [C, D, H, W] fp32, uint8 mask [C, D, H, W]). ITK is not installed here: the tie rule between
+    components of equal size is this project's (see keep_largest_component)."""
+    x = _stacked(probabilities)
+    be, conn = _be(x, _backend), _connectivity(connectivity)
+    mean, mask = be.ensemble_threshold(x, threshold)
+    if not keep_largest and min_size <= 1:
+        return mean, mask
+    out, _ = be.cc_filter(mask, be.cc_label(mask, conn), keep_largest, min_size)
+    return mean, out

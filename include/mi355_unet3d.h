@@ -471,6 +471,28 @@ int mi355_adam_step(float* param, const float* grad, float* exp_avg, float* exp_
 /* Library / build identification: returns e.g. "mi355_unet3d gfx950 <version>". */
 const char* mi355_version(void);
 
+/* ---- ensemble mean, connected components, largest-component cleanup (csrc/components.hip) -------------------------------------------
+ * The last step of the reference's complete inference pipeline, examples/sppin/process.py:258-274: np.mean over the cross-validation
+ * models' sigmoid outputs, SimpleITK.BinaryThreshold(lowerThreshold=0.5), ConnectedComponent, RelabelComponent(sortByObjectSize=True),
+ * == 1. All functions enqueue on `stream` and return: no host synchronisation, allocation or copy inside.
+ *
+ * mi355_ensemble_threshold: probs fp32 [m][elems] -> mean fp32 [elems] (sum in index order 0 .. m-1, then a division by m) and / or
+ *   uint8 mask = mean >= threshold (INCLUSIVE, as BinaryThreshold's lower bound is; mi355_postprocess decodes with >). m == 1 is the
+ *   plain threshold. At least one of mean / mask is given.
+ * mi355_cc_label: uint8 mask [c][d][h][w] (nonzero = foreground), every channel on its own -> int32 labels [c][d][h][w]: 0 = background,
+ *   otherwise 1 + the smallest linear index (z*h + y)*w + x of any voxel of the component (independent of scheduling: bitwise
+ *   reproducible). connectivity 6 (faces) or 26 (faces + edges + corners) = ITK's fullyConnected false / true. d*h*w <= 2^31 - 2.
+ *   Three launches whatever the data.
+ * mi355_cc_filter: out[v] = mask[v] && size(component of v) >= min_size && (!keep_largest || component of v is the channel's largest);
+ *   labels as written by mi355_cc_label. Largest: most voxels, ties -> the smaller label (the component met first in raster order).
+ *   stats (or NULL): int32 [c][3] = number of components, size of the largest, label of the largest (0, 0, 0 for an empty channel).
+ *   ws: mi355_cc_workspace(c, d, h, w) bytes. Five launches whatever the data. */
+int mi355_ensemble_threshold(const float* probs, int32_t m, int64_t elems, float threshold, float* mean, uint8_t* mask, void* stream);
+size_t mi355_cc_workspace(int32_t c, int32_t d, int32_t h, int32_t w);
+int mi355_cc_label(const uint8_t* mask, int32_t c, int32_t d, int32_t h, int32_t w, int32_t connectivity, int32_t* labels, void* stream);
+int mi355_cc_filter(const uint8_t* mask, const int32_t* labels, int32_t c, int32_t d, int32_t h, int32_t w, int32_t keep_largest,
+                    int64_t min_size, uint8_t* out, int32_t* stats, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -313,6 +313,22 @@ static inline double atomicAdd(double* p, double v) {
   return old;
 }
 static inline unsigned atomicAdd(unsigned* p, unsigned v) { return __atomic_fetch_add(p, v, __ATOMIC_RELAXED); }
+// integer atomics (csrc/components.hip): real host atomics -- the blocks of a launch run on several OS threads
+static inline int atomicAdd(int* p, int v) { return __atomic_fetch_add(p, v, __ATOMIC_RELAXED); }
+static inline int atomicMin(int* p, int v) {
+  int old = __atomic_load_n(p, __ATOMIC_RELAXED);
+  while (old > v && !__atomic_compare_exchange_n(p, &old, v, true, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {}
+  return old;
+}
+static inline int atomicCAS(int* p, int expected, int desired) {
+  __atomic_compare_exchange_n(p, &expected, desired, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED);
+  return expected;
+}
+static inline unsigned long long atomicMax(unsigned long long* p, unsigned long long v) {
+  unsigned long long old = __atomic_load_n(p, __ATOMIC_RELAXED);
+  while (old < v && !__atomic_compare_exchange_n(p, &old, v, true, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {}
+  return old;
+}
 
 #define LAUNCH(kernel, grid, block, lds, stream, ...) \
   emu::launch((grid), (block), (lds), [=]() { kernel(__VA_ARGS__); }, #kernel)
@@ -325,7 +341,19 @@ static inline unsigned atomicAdd(unsigned* p, unsigned v) { return __atomic_fetc
 #define PIN_IN_VGPR(v) ((void)0)
 #define PIN_IN_SGPR(v) ((void)0)
 typedef unsigned long long LaneMask;
-static inline LaneMask emu_lane_mask(bool c) { LaneMask m = 0; for (int l = 0; l < 64; ++l) m |= (LaneMask)(emu_shfl((int)c, l) & 1) << l; return m; }
+// every lane of the wave publishes its bit, one wave barrier, every lane gathers all 64 (lanes beyond a short last wave read as 0)
+static inline LaneMask emu_lane_mask(bool c) {
+  emu::BlockState* bs = emu::g_bs;
+  const int t = emu::flat_tid(), wbase = (t / 64) * 64;
+  const int n = (int)std::min(64u, bs->nthreads - (unsigned)wbase);
+  const int bit = c ? 1 : 0;
+  memcpy(&bs->xchg[t], &bit, sizeof(int));
+  emu::wave_barrier();
+  LaneMask m = 0;
+  for (int l = 0; l < n; ++l) { int b; memcpy(&b, &bs->xchg[wbase + l], sizeof(int)); m |= (LaneMask)(b & 1) << l; }
+  emu::wave_barrier();
+  return m;
+}
 #define LANE_MASK(cond) emu_lane_mask(cond)
 #define LANE_IN_MASK(m) ((((m) >> (emu::flat_tid() % 64)) & 1ull) != 0)
 // LDS-DMA (global_load_lds_dwordx4 + counted s_waitcnt vmcnt(n)). Two models, MI355_EMU_DMA=late (default) | early:
