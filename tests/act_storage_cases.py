@@ -51,8 +51,14 @@ def acts(be, t, ld=None, c0=0):
 
 def out_pair(be, shape5, ld=None, c0=0, fill=0.0):
     n, c, d, h, w = shape5
-    t = torch.full((n, c, d, h, w), fill)
-    return acts(be, t, ld, c0)
+    if C.OUT_FILL is None:
+        return acts(be, torch.full((n, c, d, h, w), fill), ld, c0)
+    # poisoned: the 16-bit twin gets its own type's poison (a NaN converted from fp32 is a NaN too, but not the named pattern)
+    a32 = C.to_act(be, C.out_host((n, c, d, h, w), fill), ld, c0)
+    t16 = C.out_host((n, c, d, h, w), fill, BF)
+    buf16 = a32.buf.to(BF)
+    buf16[..., c0:c0 + c] = t16.permute(0, 2, 3, 4, 1).to(buf16.device)
+    return a32, ops.Act(buf16.contiguous(), a32.c0, a32.c)
 
 
 def stored_ok(a16, a32):
@@ -98,7 +104,7 @@ def case_pointwise(be):
     d16 = be.empty_act(2, 3, 4, 5, 4, dtype=BF)
     be.ncdhw_to_ndhwc(C.dev(be, src), d16)
     assert torch.equal(d16.tensor().cpu().permute(0, 4, 1, 2, 3), src.to(BF))
-    back = torch.empty(2, 4, 3, 4, 5, device=be.device)
+    back = C.out_host((2, 4, 3, 4, 5), None).to(be.device)
     be.ndhwc_to_ncdhw(d16, back)
     assert torch.equal(back.cpu(), src.to(BF).float())
     return errs
@@ -117,7 +123,7 @@ def case_norm(be, n=2, c=16, dhw=(5, 6, 7), groups=8, slope=0.0):
     dx32, dx16 = out_pair(be, (n, c, *dhw))
     gr = []
     for x, dA, ad, dx, st in ((x32, dA32, ad32, dx32, st32), (x16, dA16, ad16, dx16, st16)):
-        dg, db = torch.empty(c, device=be.device), torch.empty(c, device=be.device)
+        dg, db = C.out_host((c,), None).to(be.device), C.out_host((c,), None).to(be.device)
         be.gn_act_bwd(x, dA, dx, groups, slope, gamma, st[0], st[1], st[2], dg, db, addend=ad)
         gr.append((dg.cpu(), db.cpu()))
     errs["dx"] = stored_ok(dx16, dx32)
@@ -130,14 +136,14 @@ def case_proj(be):
     g = torch.Generator().manual_seed(3)
     x32, x16 = acts(be, bf16_values((2, 32, 4, 5, 6), g))
     w = C.dev(be, torch.randn(3, 32, generator=g) * 0.2)
-    lo32 = torch.empty(2, 3, 4, 5, 6, device=be.device); lo16 = torch.empty_like(lo32)
+    lo32 = C.out_host((2, 3, 4, 5, 6), None).to(be.device); lo16 = C.out_host((2, 3, 4, 5, 6), None).to(be.device)
     be.proj_fwd(x32, w, None, lo32); be.proj_fwd(x16, w, None, lo16)
     errs = {"logits": C.rel_err(lo16, lo32)}
     dz = C.dev(be, torch.randn(2, 3, 4, 5, 6, generator=g))
     dx32, dx16 = out_pair(be, (2, 32, 4, 5, 6))
     dws = []
     for x, dx in ((x32, dx32), (x16, dx16)):
-        dw = torch.empty(3, 32, device=be.device)
+        dw = C.out_host((3, 32), None).to(be.device)
         be.proj_bwd(x, w, dz, dx, dw, None)
         dws.append(dw.cpu())
     errs["dx"] = stored_ok(dx16, dx32)
@@ -158,9 +164,12 @@ def _conv_both(be, t, w, mode, kd, yshape, call_kw, x_ld=None, x_c0=0, res=None,
         ydt = torch.float32 if (kind == "f32" or y16_is_f32) else BF
         n, c, d, h, wd = yshape
         ld = y_ld or c
+        # zero=True: the ConvTranspose window case writes into a pre-zeroed larger tensor (the kernel owns the window only)
         buf = (torch.zeros if zero else torch.empty)(n, d, h, wd, ld, dtype=ydt, device=be.device)
         if not zero:
             buf.fill_(3.0)
+            if C.OUT_FILL is not None:
+                buf[..., y_c0:y_c0 + c] = C.out_host((n, d, h, wd, c), 3.0, ydt).to(be.device)
         y = ops.Act(buf, y_c0, c)
         kw = dict(call_kw)
         if res is not None:
@@ -190,7 +199,7 @@ def _conv_both(be, t, w, mode, kd, yshape, call_kw, x_ld=None, x_c0=0, res=None,
             c = y16.c
             res_ = []
             for partials in (ret, None):
-                dg, db = torch.empty(c, device=be.device), torch.empty(c, device=be.device)
+                dg, db = C.out_host((c,), None).to(be.device), C.out_host((c,), None).to(be.device)
                 dx = be.empty_act(*y16.shape, dtype=BF)
                 be.gn_act_bwd(gx16, y16, dx, groups, 0.0, None, st[0], st[1], st[2], dg, db, partials=partials)
                 res_.append((dg.cpu(), db.cpu()))
@@ -268,7 +277,7 @@ def case_first_layer(be, dhw=(6, 9, 10), cout=32):
     dy32, dy16 = acts(be, bf16_values((n, cout, *dhw), g))
     dws = []
     for dy in (dy32, dy16):
-        dw = torch.empty(cout, 4, 3, 3, 3, device=be.device)
+        dw = C.out_host((cout, 4, 3, 3, 3), None).to(be.device)
         be.conv_wgrad(x32, dy, dw, 3, 1, in_mode=ops.IN_AFFINE_ACT, scale=st[1], shift=st[2])
         dws.append(dw.cpu())
     out["wgrad"] = C.rel_err(dws[1], dws[0])
@@ -279,8 +288,8 @@ def case_first_layer(be, dhw=(6, 9, 10), cout=32):
         res = []
         for dy in (dy32, dy16):
             assert be.c4_bwd_supported(x32, dy, ops.IN_AFFINE_ACT, 0.0, st[1], st[2])
-            dw = torch.full((cout, 4, 3, 3, 3), 7.0, device=be.device)
-            dg, db = torch.full((4,), 7.0, device=be.device), torch.full((4,), 7.0, device=be.device)
+            dw = C.out_host((cout, 4, 3, 3, 3), 7.0).to(be.device)
+            dg, db = C.out_host((4,), 7.0).to(be.device), C.out_host((4,), 7.0).to(be.device)
             be.c4_bwd(x32, dy, be.pack_weight(C.dev(be, w), 1), dw, 4, gam, st[0], st[1], st[2], dg, db)
             res.append((dw.cpu(), dg.cpu(), db.cpu()))
         out["c4bwd_dw"], out["c4bwd_dgamma"], out["c4bwd_dbeta"] = (C.rel_err(a, b) for a, b in zip(res[1], res[0]))
@@ -302,7 +311,7 @@ def case_wgrad(be, kd, stride, cin, cout, dhw, norm=False, n=1):
         kw = dict(in_mode=ops.IN_AFFINE_ACT, scale=st[1], shift=st[2])
     dws = []
     for x, dy in ((x32, dy32), (x16, dy16)):
-        dw = torch.full((cout, cin, kd, kd, kd), 3.0, device=be.device)
+        dw = C.out_host((cout, cin, kd, kd, kd), 3.0).to(be.device)
         be.conv_wgrad(x, dy, dw, kd, stride, **kw)
         dws.append(dw.cpu())
     return {"dw": C.rel_err(dws[1], dws[0])}

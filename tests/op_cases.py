@@ -19,6 +19,38 @@ ops = importlib.import_module("3dunetcnn_amd.ops")
 Act = ops.Act
 TOL = 1e-3
 
+# What the outputs a case pre-makes for a kernel to overwrite (y, dx, dw, dgamma / dbeta, ...) hold before the call. None: what they always
+# held (zeros, a constant, uninitialised memory). A 32-bit pattern (QNAN, ONES): every element is that poison (tests/scratch_guard.py sets
+# it for its guarded runs: a kernel that accumulates where it should store, or skips a slot, then shows). act_storage_cases reads it too;
+# augment_cases / components_cases pre-make no output (theirs are allocated by 3dunetcnn_amd.ops, which the harness reaches directly).
+OUT_FILL = None
+QNAN = 0x7fc00000            # quiet NaN as fp32; bf16 0x7fc0, fp16 0x7e00
+ONES = 0xffffffff            # NaN as fp32 / bf16 / fp16, -1 as int32 / int16, 255 as uint8
+
+
+def poison_bytes(u8, dtype, word):
+    """Fills the 1-D uint8 tensor `u8` (the bytes of a tensor of `dtype`, 4-byte aligned) with the poison `word`: 4- and 8-byte types get
+    the word itself, 16-bit types its upper half (fp16: its own quiet NaN for QNAN), 8-bit types its top byte."""
+    if u8.numel() == 0:
+        return
+    if dtype.itemsize == 2:
+        v = 0x7e00 if (dtype == torch.float16 and word == QNAN) else word >> 16
+        u8.view(torch.int16).fill_(v - (1 << 16) if v >= 1 << 15 else v)
+    elif dtype.itemsize % 4 == 0:
+        u8.view(torch.int32).fill_(word - (1 << 32) if word >= 1 << 31 else word)
+    else:
+        u8.fill_(word >> 24)
+
+
+def out_host(shape, value=0.0, dtype=torch.float32):
+    """Host tensor for an output a kernel must overwrite completely: `value` everywhere (None: uninitialised) or, under OUT_FILL, poison."""
+    shape = tuple(shape)
+    if OUT_FILL is None:
+        return torch.empty(shape, dtype=dtype) if value is None else torch.full(shape, value, dtype=dtype)
+    t = torch.empty(shape, dtype=dtype)
+    poison_bytes(t.view(-1).view(torch.uint8), dtype, OUT_FILL)
+    return t
+
 
 def rel_err(a, b):
     a = a.detach().cpu().double()
@@ -106,7 +138,7 @@ def case_conv_fwd(be, n, cin, cout, dhw, kd=3, stride=1, norm=False, groups=None
     ref = O.conv_block(x, wt, stride, pad, normspec, b, res, cs)
 
     xa = to_act(be, x, xld)
-    ya = to_act(be, torch.zeros(n, cout, od, oh, ow), yld, yc0)
+    ya = to_act(be, out_host((n, cout, od, oh, ow)), yld, yc0)
     wp = be.pack_weight(dev(be, wt), 0)
     kw = {}
     if norm:
@@ -135,7 +167,7 @@ def case_conv_dgrad(be, n, cin, cout, dhw, stride=1, seed=1, residual=False):
     dy = torch.randn(y.shape, generator=g)
     (dx_ref,) = torch.autograd.grad(y, x, dy)
     dya = to_act(be, dy)
-    dxa = to_act(be, torch.zeros(n, cin, d, h, w))
+    dxa = to_act(be, out_host((n, cin, d, h, w)))
     wpd = be.pack_weight(dev(be, wt), 1)
     res = torch.randn(n, cin, d, h, w, generator=g) if residual else None
     ra = to_act(be, res) if residual else None
@@ -161,7 +193,8 @@ def case_tconv3(be, n, cin, cout, dhw, pad_to=None, seed=12):
     if pad_to:
         ref = F.pad(ref, [v for t, o, f in reversed(list(zip(tgt, od, off))) for v in (f, t - o - f)])
     xa = to_act(be, x)
-    ya = to_act(be, torch.zeros(n, cout, *tgt))
+    # pad_to: the output is a window of a PRE-ZEROED larger tensor (unet.py allocates it with zeros_act; the kernel writes the window only)
+    ya = to_act(be, torch.zeros(n, cout, *tgt) if pad_to else out_host((n, cout, *tgt)))
     be.conv_fwd(xa, be.pack_weight(dev(be, wt), 2), ya, 3, 1, pad=1, in_mode=ops.IN_ZERO_INSERT, bias=dev(be, b), off=off, out_dhw=od)
     return rel_err(from_act(ya), ref)
 
@@ -183,7 +216,7 @@ def case_conv_wgrad(be, n, cin, cout, dhw, kd=3, stride=1, norm=False, slope=0.0
     dy = torch.randn(y.shape, generator=g)
     (dw_ref,) = torch.autograd.grad(y, wt, dy)
     xa, dya = to_act(be, x), to_act(be, dy)
-    dw = torch.full(wt.shape, 3.0, dtype=torch.float32, device=be.device)
+    dw = out_host(wt.shape, 3.0).to(be.device)
     kw = {}
     if norm:
         mr, sc, sh = be.gn_stats(xa, groups, 1e-5, dev(be, gamma), dev(be, beta))
@@ -212,14 +245,14 @@ def case_tconv2(be, n, cin, cout, dhw, norm=True, yld=None, seed=9):
         mr, sc, sh = be.gn_stats(xa, cin, 1e-5, dev(be, gamma), dev(be, beta))
         kw = dict(in_mode=ops.IN_AFFINE_ACT, slope=0.01, scale=sc, shift=sh)
     w1 = dev(be, wt.detach().permute(2, 3, 4, 1, 0).reshape(8 * cout, cin, 1, 1, 1))
-    ya = to_act(be, torch.zeros(n, cout, 2 * d, 2 * h, 2 * w), yld)
+    ya = to_act(be, out_host((n, cout, 2 * d, 2 * h, 2 * w)), yld)
     be.conv_fwd(xa, be.pack_weight(w1, 0), ya, 1, out_mode=ops.OUT_D2S, **kw)
     e_f = rel_err(from_act(ya), y)
     dya = to_act(be, dy, yld)
-    dxa = to_act(be, torch.zeros(n, cin, d, h, w))
+    dxa = to_act(be, out_host((n, cin, d, h, w)))
     be.conv_fwd(dya, be.pack_weight(w1, 1), dxa, 1, in_mode=ops.IN_S2D)
     e_d = rel_err(from_act(dxa), a.grad)
-    dw1 = torch.full((8 * cout, cin), 3.0, dtype=torch.float32, device=be.device)
+    dw1 = out_host((8 * cout, cin), 3.0).to(be.device)
     be.conv_wgrad(xa, dya, dw1, 1, out_mode=ops.OUT_D2S, **kw)
     dw = dw1.view(2, 2, 2, cout, cin).permute(4, 3, 0, 1, 2)
     return dict(fwd=e_f, dgrad=e_d, wgrad=rel_err(dw, wt.grad))
@@ -246,9 +279,9 @@ def case_conv_cat_slope(be, n, c_up, c_skip, cout, dhw, stride=1, seed=10):
     shift = torch.cat((0 * ones, sh), 1).contiguous()
     slope = torch.cat((ones[0], torch.full((c_skip,), 0.01, device=be.device))).contiguous()
     kw = dict(in_mode=ops.IN_AFFINE_ACT, slope=0.01, scale=scale, shift=shift, in_slope=slope)
-    ya = to_act(be, torch.zeros_like(y.detach()))
+    ya = to_act(be, out_host(y.shape))
     be.conv_fwd(cat, be.pack_weight(dev(be, wt.detach()), 0), ya, 3, stride, **kw)
-    dw = torch.empty(wt.shape, dtype=torch.float32, device=be.device)
+    dw = out_host(wt.shape, None).to(be.device)
     be.conv_wgrad(cat, to_act(be, dy), dw, 3, stride, **kw)
     return dict(fwd=rel_err(from_act(ya), y), wgrad=rel_err(dw, dw_ref))
 
@@ -275,9 +308,9 @@ def case_gn(be, n, c, dhw, groups, slope=0.0, ld=None, seed=3, offset=0.4):
     rstd_ref = (xg.var(-1, unbiased=False) + 1e-5).rsqrt()
     e_stats = max(rel_err(mr[..., 0], mean_ref), rel_err(mr[..., 1], rstd_ref))
     dAa = to_act(be, dA)
-    dxa = to_act(be, torch.zeros_like(dA))
-    dgam = torch.empty(c, device=be.device)
-    dbet = torch.empty(c, device=be.device)
+    dxa = to_act(be, out_host(dA.shape))
+    dgam = out_host((c,), None).to(be.device)
+    dbet = out_host((c,), None).to(be.device)
     be.gn_act_bwd(xa, dAa, dxa, groups, slope, dev(be, gamma.detach()), mr, sc, sh, dgam, dbet, addend=to_act(be, add))
     return dict(stats=e_stats, dx=rel_err(from_act(dxa), dx_ref), dgamma=rel_err(dgam, dg_ref), dbeta=rel_err(dbet, db_ref))
 
@@ -305,7 +338,7 @@ def case_conv_moments(be, n, cin, cout, dhw, stride=1, norm=True, residual=False
     res = torch.randn(n, cout, od, oh, ow, generator=g) + 3.0 if residual else None      # |mean| >> std of the conv term
     cs = (torch.rand(n, cout, generator=g) > 0.3).float() * 1.25 if chscale else None
     ref = O.conv_block(x, wt, stride, 1, normspec, None, res, cs)
-    ya = to_act(be, torch.zeros(n, cout, od, oh, ow), yld, yc0)
+    ya = to_act(be, out_host((n, cout, od, oh, ow)), yld, yc0)
     be.conv_fwd(xa, be.pack_weight(dev(be, wt), 0), ya, 3, stride, 1, residual=to_act(be, res) if residual else None, chscale=dev(be, cs),
                 moments=True, **kw)
     assert rel_err(from_act(ya), ref) < ytol
@@ -340,6 +373,8 @@ def case_cat_moments(be, n, c_up, c_skip, dhw, seed=14):
     x = torch.randn(n, 8, d, h, w, generator=g)
     wt = torch.randn(c_skip, 8, 3, 3, 3, generator=g) * 0.1
     skip = F.conv3d(x, wt, None, padding=1)
+    # zeros, not OUT_FILL: the buffer is written in two halves, the first one by the host copy below -- to_act would have to know the split
+    # to poison the conv half only. The conv half is covered by case_conv_moments(yld=, yc0=): a slice of a wider buffer.
     cat = to_act(be, torch.zeros(n, c_up + c_skip, d, h, w))
     cat.tensor()[..., :c_up] = up.permute(0, 2, 3, 4, 1).to(be.device)
     sl_up, sl_skip = cat.slice(0, c_up), cat.slice(c_up, c_skip)
@@ -371,16 +406,16 @@ def case_gn_bwd_fused(be, n, cin, cout, dhw, groups=None, slope=0.0, expect_fuse
     dx_ref, dg_ref, db_ref = torch.autograd.grad(y, (x, gamma, beta), dy.double())
     xa = to_act(be, x.detach().float())
     st = be.gn_stats(xa, groups, 1e-5, dev(be, gamma.detach().float()), dev(be, beta.detach().float()))
-    dA = to_act(be, torch.zeros(n, cin, d, h, w))
+    dA = to_act(be, out_host((n, cin, d, h, w)))
     parts = be.conv_fwd(to_act(be, dy), be.pack_weight(dev(be, wt.float()), 1), dA, 3, 1, 1, gnb=(xa, st, groups, slope))
     assert (parts is not None) == expect_fused
-    dgam, dbet = torch.empty(cin, device=be.device), torch.empty(cin, device=be.device)
+    dgam, dbet = out_host((cin,), None).to(be.device), out_host((cin,), None).to(be.device)
     dA_raw = dA.tensor().clone()
     be.gn_act_bwd(xa, dA, dA, groups, slope, dev(be, gamma.detach().float()), st[0], st[1], st[2], dgam, dbet, partials=parts)
     if compare_unfused:
         # reduced-precision conv arithmetic: compare with the unfused norm backward applied to the SAME dA (the sums' own accuracy)
         dA2 = Act(dA_raw.contiguous(), 0, cin)
-        dg2, db2 = torch.empty(cin, device=be.device), torch.empty(cin, device=be.device)
+        dg2, db2 = out_host((cin,), None).to(be.device), out_host((cin,), None).to(be.device)
         be.gn_act_bwd(xa, dA2, dA2, groups, slope, dev(be, gamma.detach().float()), st[0], st[1], st[2], dg2, db2)
         return dict(dx=rel_err(from_act(dA), from_act(dA2)), dgamma=rel_err(dgam, dg2.cpu()), dbeta=rel_err(dbet, db2.cpu()))
     return dict(dx=rel_err(from_act(dA), dx_ref), dgamma=rel_err(dgam, dg_ref), dbeta=rel_err(dbet, db_ref))
@@ -403,8 +438,8 @@ def case_c4_bwd(be, n, dhw, groups=4, slope=0.0, seed=21, xld=None, dyld=None):
     mr, sc, sh = be.gn_stats(xa, groups, 1e-5, gam, bet)
     assert be.c4_bwd_supported(xa, dya, ops.IN_AFFINE_ACT, slope, sc, sh)
     wp = be.pack_weight(dev(be, wt.detach().float()), 1)
-    dw = torch.full((32, 4, 3, 3, 3), 7.0, device=be.device)
-    dgam, dbet = torch.full((4,), 7.0, device=be.device), torch.full((4,), 7.0, device=be.device)
+    dw = out_host((32, 4, 3, 3, 3), 7.0).to(be.device)
+    dgam, dbet = out_host((4,), 7.0).to(be.device), out_host((4,), 7.0).to(be.device)
     be.c4_bwd(xa, dya, wp, dw, groups, gam, mr, sc, sh, dgam, dbet, slope=slope)
     return dict(dw=rel_err(dw, dw_ref), dgamma=rel_err(dgam, dg_ref), dbeta=rel_err(dbet, db_ref))
 
@@ -417,11 +452,11 @@ def case_upsample(be, n, c, lo_dhw, target_dhw, c_skip=8, seed=4):
     (dlo_ref,) = torch.autograd.grad(up, lo, dcat[:, :c])
     off = tuple((t - 2 * l) // 2 for t, l in zip(target_dhw, lo_dhw))
     loa = to_act(be, lo.detach())
-    cat = to_act(be, torch.zeros(n, c, *target_dhw), ld=c + c_skip, c0=0)
+    cat = to_act(be, out_host((n, c, *target_dhw)), ld=c + c_skip, c0=0)
     be.upsample2x_fwd(loa, cat, off)
     e_f = rel_err(from_act(cat), up)
     dcata = to_act(be, dcat).slice(0, c)
-    dloa = to_act(be, torch.zeros_like(lo.detach()))
+    dloa = to_act(be, out_host(lo.shape))
     be.upsample2x_bwd(dcata, dloa, off)
     return dict(fwd=e_f, bwd=rel_err(from_act(dloa), dlo_ref))
 
@@ -447,11 +482,11 @@ def case_proj(be, n, cin, cout, dhw, bias=False, seed=5, norm=False):
     if norm:
         mr, sc, sh = be.gn_stats(xa, cin, 1e-5, dev(be, gamma), dev(be, beta))
         pk = dict(scale=sc, shift=sh, slope=0.01)
-    logits = torch.empty(n, cout, *dhw, device=be.device)
+    logits = out_host((n, cout, *dhw), None).to(be.device)
     be.proj_fwd(xa, dev(be, w.detach().reshape(cout, cin)), dev(be, b.detach()) if bias else None, logits, **pk)
-    dxa = to_act(be, torch.zeros_like(x.detach()))
-    dw = torch.empty(cout, cin, device=be.device)
-    dbias = torch.empty(cout, device=be.device) if bias else None
+    dxa = to_act(be, out_host(x.shape))
+    dw = out_host((cout, cin), None).to(be.device)
+    dbias = out_host((cout,), None).to(be.device) if bias else None
     be.proj_bwd(xa, dev(be, w.detach().reshape(cout, cin)), dev(be, dy), dxa, dw, dbias, **pk)
     out = dict(fwd=rel_err(logits, y), dx=rel_err(from_act(dxa), grads[0]), dw=rel_err(dw, grads[1].reshape(cout, cin)))
     if bias:
@@ -520,9 +555,9 @@ def case_adam(be, count, steps=3, wd=0.0, seed=7):
 def case_layout(be, n, c, dhw, seed=8):
     g = torch.Generator().manual_seed(seed)
     x = torch.randn(n, c, *dhw, generator=g)
-    a = to_act(be, torch.zeros_like(x))
+    a = to_act(be, out_host(x.shape))
     be.ncdhw_to_ndhwc(dev(be, x), a)
     e1 = rel_err(from_act(a), x)
-    back = torch.empty_like(x, device=be.device)
+    back = out_host(x.shape, None).to(be.device)
     be.ndhwc_to_ncdhw(a, back)
     return max(e1, rel_err(back, x))
