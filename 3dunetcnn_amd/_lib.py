@@ -142,7 +142,14 @@ SIGNATURES = {
     "mi355_cc_label": (ctypes.c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     "mi355_cc_filter": (ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int64, c_void_p, c_void_p,
                                        c_void_p, c_size_t, c_void_p]),
+    "mi355_seg_counts": (ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "mi355_mask_edges": (ctypes.c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "mi355_edt": (ctypes.c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_float, c_float, c_float, c_void_p, c_void_p,
+                                 c_void_p]),
+    "mi355_surface_stats": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_double, c_void_p, c_void_p, c_void_p,
+                                           c_void_p]),
 }
+SURFACE_SCRATCH_BYTES = 32832      # MI355_SURFACE_SCRATCH_BYTES of the header: scratch of mi355_surface_stats, per channel
 
 
 def bind(cdll):

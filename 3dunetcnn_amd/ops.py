@@ -802,6 +802,52 @@ class Backend:
                                        stats.data_ptr(), ws.data_ptr(), ws.numel() * 4, self.stream()), "cc_filter")
         return out, stats
 
+    # -- scoring a mask: overlap counts, edges, exact distance transform, surface distances (csrc/metrics.hip) ---------------------------
+    @staticmethod
+    def _mask_ok(m, like=None):
+        return (m.is_contiguous() and m.dtype == torch.uint8 and m.dim() == 4
+                and (like is None or (m.shape == like.shape and m.device == like.device)))
+
+    def seg_counts(self, pred, truth):
+        """pred, truth uint8 [C, D, H, W] (nonzero = foreground) -> int32 [C, 4] = (TP, FP, FN, TN) per channel."""
+        assert self._mask_ok(pred) and self._mask_ok(truth, pred)
+        counts = torch.empty(pred.shape[0], 4, dtype=torch.int32, device=pred.device)
+        check(self.lib.mi355_seg_counts(pred.data_ptr(), truth.data_ptr(), *pred.shape, counts.data_ptr(), self.stream()), "seg_counts")
+        return counts
+
+    def mask_edges(self, mask):
+        """uint8 [C, D, H, W] -> uint8 0 / 1: foreground voxels with a background face neighbour (outside the volume = background)."""
+        assert self._mask_ok(mask)
+        edges = torch.empty_like(mask)
+        check(self.lib.mi355_mask_edges(mask.data_ptr(), *mask.shape, edges.data_ptr(), self.stream()), "mask_edges")
+        return edges
+
+    def edt(self, sites, spacing=(1.0, 1.0, 1.0), invert=False, sqrt=True):
+        """Exact Euclidean distance, in units of spacing (z, y, x), from every voxel to the nearest nonzero voxel of `sites` (invert: to
+        the nearest zero voxel); +inf in a channel without one. sqrt=False: the squared distance as the kernel leaves it (integers,
+        bit-exact, for unit spacing). uint8 [C, D, H, W] -> fp32 [C, D, H, W]."""
+        assert self._mask_ok(sites) and len(spacing) == 3
+        dist2 = torch.empty(sites.shape, dtype=torch.float32, device=sites.device)
+        tmp = torch.empty(sites.shape, dtype=torch.float32, device=sites.device)
+        check(self.lib.mi355_edt(sites.data_ptr(), int(bool(invert)), *sites.shape, float(spacing[0]), float(spacing[1]), float(spacing[2]),
+                                 dist2.data_ptr(), tmp.data_ptr(), self.stream()), "edt")
+        return dist2.sqrt_() if sqrt else dist2
+
+    def surface_stats(self, edges_a, edges_b, dist2_ab, dist2_ba, percentile=95.0):
+        """Edge masks of A and B, squared distance fields to the edges of B and of A -> (fp32 [C, 8] = hd, hd_pct, asd, hd_ab, hd_ba, pct_ab,
+        pct_ba, asd_ab; int32 [C, 2] = edge voxels of A, of B). See mi355_surface_stats."""
+        assert self._mask_ok(edges_a) and self._mask_ok(edges_b, edges_a)
+        for t in (dist2_ab, dist2_ba):
+            assert t.is_contiguous() and t.dtype == torch.float32 and t.shape == edges_a.shape and t.device == edges_a.device
+        c = edges_a.shape[0]
+        out = torch.empty(c, 8, dtype=torch.float32, device=edges_a.device)
+        n = torch.empty(c, 2, dtype=torch.int32, device=edges_a.device)
+        scratch = torch.empty(c * _lib.SURFACE_SCRATCH_BYTES // 8, dtype=torch.float64, device=edges_a.device)
+        check(self.lib.mi355_surface_stats(edges_a.data_ptr(), edges_b.data_ptr(), dist2_ab.data_ptr(), dist2_ba.data_ptr(), c,
+                                           edges_a[0].numel(), float(percentile), out.data_ptr(), n.data_ptr(), scratch.data_ptr(),
+                                           self.stream()), "surface_stats")
+        return out, n
+
     def augment_batch(self, image, label, matrices, gain=None, offset=None, out_shape=None, padding="border", normalize=False):
         """Training augmentation of a batch in two launches (mi355_augment_batch). image [N, Ci, D, H, W] fp32; label None or
         [N, Cl, D, H, W] uint8 / fp32; matrices [N, 3, 4] (or [N, 12]) fp32 ON THE DEVICE: output voxel -> source voxel, (z, y, x)

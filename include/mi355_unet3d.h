@@ -493,6 +493,36 @@ int mi355_cc_label(const uint8_t* mask, int32_t c, int32_t d, int32_t h, int32_t
 int mi355_cc_filter(const uint8_t* mask, const int32_t* labels, int32_t c, int32_t d, int32_t h, int32_t w, int32_t keep_largest,
                     int64_t min_size, uint8_t* out, int32_t* stats, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- overlap counts, mask edges, exact Euclidean distance transform, surface distances (csrc/metrics.hip) ---------------------------
+ * Scoring a mask against the ground truth without leaving the device. Masks are uint8 [c][d][h][w], nonzero = foreground, every
+ * channel on its own; d*h*w <= 2^31 - 2 (as mi355_cc_label). Every buffer is the caller's and has a closed-form size: a tensor of the
+ * volume's shape, c rows of a few words, or c * MI355_SURFACE_SCRATCH_BYTES. All functions enqueue on `stream` and return; a fixed number
+ * of launches whatever the data; integer atomics only, so two calls on the same input give the same bits.
+ *
+ * mi355_seg_counts: int32 counts[c][4] = (TP, FP, FN, TN) of pred against truth. The op zeroes counts itself. Two launches.
+ * mi355_mask_edges: edges[v] = mask[v] != 0 && not all six face neighbours are foreground; a neighbour outside the volume is background
+ *   (= mask ^ scipy.ndimage.binary_erosion(mask), default structure, border_value=0). uint8 0 / 1, every voxel written. One launch.
+ * mi355_edt: dist2[v] = squared distance, in units of the spacing (sz, sy, sx), from v to the nearest voxel whose `sites` value is nonzero
+ *   (invert != 0: whose value is zero); +inf everywhere in a channel without such a voxel. Exact: separable, every line minimised over
+ *   all its candidates. With spacing (1, 1, 1) every value is an integer and bit-exact in fp32 while
+ *   (d-1)^2 + (h-1)^2 + (w-1)^2 < 2^24; larger extents are still computed, rounded. Other spacings: relative error < 5 * 2^-24.
+ *   tmp: fp32 [c][d][h][w] scratch, fully written before it is read, distinct from dist2. Spacings are finite and > 0. Three launches.
+ * mi355_surface_stats: per channel, from the edge masks of two sets A, B and the squared distance fields to the edges of B (dist2_ab,
+ *   read at the edges of A) and of A (dist2_ba, read at the edges of B), over d = sqrtf(dist2), per direction: the maximum, the mean and
+ *   the `percentile`-th percentile (numpy's default linear rule: position p = percentile / 100 * (n - 1),
+ *   v[floor(p)] + (p - floor(p)) * (v[floor(p) + 1] - v[floor(p)]); the two order statistics by an exact radix select).
+ *   out fp32 [c][8] = (hd, hd_pct, asd, hd_ab, hd_ba, pct_ab, pct_ba, asd_ab) with hd = max(hd_ab, hd_ba), hd_pct = max(pct_ab, pct_ba),
+ *   asd = (sum_ab + sum_ba) / (n_a + n_b). Both edge sets empty: every entry 0; exactly one empty: every entry +inf (this project's
+ *   convention, after what MONAI documents; not checked against a MONAI release). n int32 [c][2] = (n_a, n_b) edge voxels.
+ *   voxels = d*h*w; 0 <= percentile <= 100. scratch: c * MI355_SURFACE_SCRATCH_BYTES bytes, 8-byte aligned, zeroed by the op. Ten launches. */
+#define MI355_SURFACE_SCRATCH_BYTES 32832
+int mi355_seg_counts(const uint8_t* pred, const uint8_t* truth, int32_t c, int32_t d, int32_t h, int32_t w, int32_t* counts, void* stream);
+int mi355_mask_edges(const uint8_t* mask, int32_t c, int32_t d, int32_t h, int32_t w, uint8_t* edges, void* stream);
+int mi355_edt(const uint8_t* sites, int32_t invert, int32_t c, int32_t d, int32_t h, int32_t w, float sz, float sy, float sx,
+              float* dist2, float* tmp, void* stream);
+int mi355_surface_stats(const uint8_t* edges_a, const uint8_t* edges_b, const float* dist2_ab, const float* dist2_ba, int32_t c,
+                        int64_t voxels, double percentile, float* out, int32_t* n, void* scratch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
