@@ -30,6 +30,18 @@ class MiDiceOpts(Structure):
                 ("smooth_nr", c_float), ("smooth_dr", c_float), ("class_weight", c_void_p)]
 
 
+class MiFocalOpts(Structure):
+    """mi355_focal_opts: form (sigmoid / softmax), gamma, alpha, counted channels, target kind, reduction, class weights."""
+    _fields_ = [("mode", c_int32), ("target_kind", c_int32), ("include_background", c_int32), ("reduction", c_int32),
+                ("has_alpha", c_int32), ("gamma", c_float), ("alpha", c_float), ("class_weight", c_void_p)]
+
+
+class MiTverskyOpts(Structure):
+    """mi355_tversky_opts: the monai TverskyLoss options (the activation / target / reduction codes are the Dice ones)."""
+    _fields_ = [("activation", c_int32), ("target_kind", c_int32), ("batch", c_int32), ("include_background", c_int32),
+                ("reduction", c_int32), ("alpha", c_float), ("beta", c_float), ("smooth_nr", c_float), ("smooth_dr", c_float)]
+
+
 class MiConvDesc(Structure):
     _fields_ = [("kd", c_int32), ("stride", c_int32), ("pad", c_int32), ("in_mode", c_int32),
                 ("act_slope", c_float),
@@ -134,6 +146,12 @@ SIGNATURES = {
     "mi355_ce_workspace": (c_size_t, [c_int64]),
     "mi355_ce_fwd_bwd": (ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int64, c_int32, c_float, c_void_p, c_int32,
                                         c_void_p, c_int32, c_float, c_void_p, c_size_t, c_void_p]),
+    "mi355_focal_fwd_bwd": (ctypes.c_int, [POINTER(MiFocalOpts), c_void_p, c_void_p, c_int32, c_int32, c_int64, c_float, c_void_p, c_int32,
+                                           c_void_p, c_int32, c_float, c_void_p, c_size_t, c_void_p]),
+    "mi355_tversky_forward": (ctypes.c_int, [POINTER(MiTverskyOpts), c_void_p, c_void_p, c_int32, c_int32, c_int64, c_void_p, c_void_p, c_size_t,
+                                             c_void_p]),
+    "mi355_tversky_backward": (ctypes.c_int, [POINTER(MiTverskyOpts), c_void_p, c_void_p, c_int32, c_int32, c_int64, c_void_p, c_int32, c_void_p,
+                                              c_void_p, c_void_p]),
     "mi355_adam_step": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_double, c_double, c_double, c_double,
                                        c_double, c_int32, c_float, c_void_p]),
     "mi355_version": (c_char_p, []),
@@ -150,6 +168,7 @@ SIGNATURES = {
                                            c_void_p]),
 }
 SURFACE_SCRATCH_BYTES = 32832      # MI355_SURFACE_SCRATCH_BYTES of the header: scratch of mi355_surface_stats, per channel
+FOCAL_SCRATCH_BYTES = 4096         # MI355_FOCAL_SCRATCH_BYTES of the header: the block partials of mi355_focal_fwd_bwd
 
 
 def bind(cdll):

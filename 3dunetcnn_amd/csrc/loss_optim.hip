@@ -382,6 +382,90 @@ extern "C" int mi355_dice_ex_backward(const mi355_dice_opts* o, const float* log
   return LAUNCH_CHECK();
 }
 
+// ---- Tversky (monai.losses.TverskyLoss) on the extended Dice passes: the same three sums, another finaliser ----
+// tp = I, fp = P - I, fn = Y - I:  f = 1 - (I + snr) / D,  D = (1 - alpha - beta) I + alpha P + beta Y + sdr
+// df/dp = -[y D - (I + snr)((1 - alpha - beta) y + alpha)] / D^2 = -a y + b: the (a, b) pair dice_ex_grad_kernel consumes (squared off).
+// c0 / reduction / the layout of loss[] and coef[]: as dice_finalize_kernel, variant 0.
+__global__ void tversky_finalize_kernel(const float* ws, int B, int N, int C, int batch, float alpha, float beta, float snr, float sdr,
+                                        int c0, float* stats, float* coef, float* loss, int reduction) {
+  __shared__ double sums[3 * 1024];
+  __shared__ double fsum[256];
+  const int NC = N * C;
+  for (int i = threadIdx.x; i < NC; i += blockDim.x) {
+    double a = 0.0, b = 0.0, c = 0.0;
+    for (int k = 0; k < B; ++k) { const float* p = ws + ((size_t)i * B + k) * 3; a += (double)p[0]; b += (double)p[1]; c += (double)p[2]; }
+    sums[3 * i] = a; sums[3 * i + 1] = b; sums[3 * i + 2] = c;
+    stats[3 * i] = (float)a; stats[3 * i + 1] = (float)b; stats[3 * i + 2] = (float)c;
+  }
+  __syncthreads();
+  double f = 0.0;
+  const int Ce = C - c0;
+  const int K = reduction != 0 ? 1 : (batch ? Ce : N * Ce);
+  const double rest = 1.0 - (double)alpha - (double)beta;
+  for (int i = threadIdx.x; i < NC; i += blockDim.x) {
+    const int c = i % C;
+    if (c < c0) { coef[2 * i] = 0.f; coef[2 * i + 1] = 0.f; continue; }
+    double I = 0.0, P = 0.0, Y = 0.0;
+    if (batch) {
+      for (int n = 0; n < N; ++n) { I += sums[3 * (n * C + c)]; P += sums[3 * (n * C + c) + 1]; Y += sums[3 * (n * C + c) + 2]; }
+    } else { I = sums[3 * i]; P = sums[3 * i + 1]; Y = sums[3 * i + 2]; }
+    const double num = I + (double)snr;
+    const double den = rest * I + (double)alpha * P + (double)beta * Y + (double)sdr;
+    coef[2 * i] = (float)((den - num * rest) / (den * den) / K);
+    coef[2 * i + 1] = (float)((double)alpha * num / (den * den) / K);
+    const double term = 1.0 - num / den;
+    if (!batch || i < C) {
+      if (reduction == 2) loss[batch ? c - c0 : (i / C) * Ce + c - c0] = (float)term;
+      else f += term / K;
+    }
+  }
+  fsum[threadIdx.x] = f;
+  __syncthreads();
+  for (int s = blockDim.x / 2; s > 0; s >>= 1) { if ((int)threadIdx.x < s) fsum[threadIdx.x] += fsum[threadIdx.x + s]; __syncthreads(); }
+  if (threadIdx.x == 0 && reduction != 2) loss[0] = (float)fsum[0];
+}
+
+static int tversky_check(const mi355_tversky_opts* o, int32_t n, int32_t c, int64_t voxels) {
+  if (!o || n <= 0 || c <= 0 || voxels <= 0) return MI355_EINVAL;
+  if (o->activation < MI355_DICE_ACT_NONE || o->activation > MI355_DICE_ACT_SOFTMAX) return MI355_EINVAL;
+  if (o->target_kind < MI355_DICE_TARGET_F32 || o->target_kind > MI355_DICE_TARGET_LABELS) return MI355_EINVAL;
+  if (o->reduction < MI355_DICE_REDUCE_MEAN || o->reduction > MI355_DICE_REDUCE_NONE) return MI355_EINVAL;
+  if (!(o->alpha == o->alpha) || !(o->beta == o->beta)) return MI355_EINVAL;                        // NaN
+  if (!o->include_background && c < 2) return MI355_EINVAL;
+  if (c > DICE_MAX_C || (size_t)n * c > 1024) return MI355_EUNSUPPORTED;
+  return MI355_OK;
+}
+
+extern "C" int mi355_tversky_forward(const mi355_tversky_opts* o, const float* logits, const void* target, int32_t n, int32_t c, int64_t voxels,
+                                     float* loss, void* ws, size_t ws_bytes, void* stream) {
+  int rc = tversky_check(o, n, c, voxels); if (rc) return rc;
+  if (!logits || !target || !loss || !ws) return MI355_EINVAL;
+  if (ws_bytes < mi355_dice_workspace(n, c, voxels)) return MI355_EWORKSPACE;
+  const int NC = n * c, B = dice_blocks(voxels);
+  float* part = (float*)ws; float* stats = part + (size_t)NC * B * 3; float* coef = stats + (size_t)NC * 3;
+  LAUNCH(dice_ex_partial_kernel, dim3(B, n), dim3(256), 0, stream, logits, target, o->target_kind, (long long)voxels, c, o->activation, 0, part);
+  rc = LAUNCH_CHECK(); if (rc) return rc;
+  LAUNCH(tversky_finalize_kernel, dim3(1), dim3(256), 0, stream, (const float*)part, B, n, c, o->batch, o->alpha, o->beta, o->smooth_nr,
+         o->smooth_dr, o->include_background ? 0 : 1, stats, coef, loss, o->reduction);
+  return LAUNCH_CHECK();
+}
+
+extern "C" int mi355_tversky_backward(const mi355_tversky_opts* o, const float* logits, const void* target, int32_t n, int32_t c, int64_t voxels,
+                                      const float* upstream, int32_t n_upstream, float* dlogits, const void* ws, void* stream) {
+  int rc = tversky_check(o, n, c, voxels); if (rc) return rc;
+  if (!logits || !target || !dlogits || !ws) return MI355_EINVAL;
+  const int ce = c - (o->include_background ? 0 : 1);
+  const int terms = o->reduction == MI355_DICE_REDUCE_NONE ? (o->batch ? ce : n * ce) : 1;
+  if (upstream && n_upstream != terms) return MI355_EINVAL;
+  const int NC = n * c, B = dice_blocks(voxels);
+  const float* coef = (const float*)ws + (size_t)NC * B * 3 + (size_t)NC * 3;
+  const long long total = (long long)n * voxels;
+  long long grid = (total + 255) / 256; if (grid > 16384) grid = 16384;
+  LAUNCH(dice_ex_grad_kernel, dim3((unsigned)grid), dim3(256), 0, stream, logits, target, o->target_kind, (long long)voxels, n, c, o->activation,
+         0, coef, upstream, n_upstream, o->batch, o->include_background ? 0 : 1, dlogits);
+  return LAUNCH_CHECK();
+}
+
 __global__ void adam_kernel(float* p, const float* g, float* m, float* v, long long count, float step_size, float b1, float omb1, float b2,
                             float omb2, float eps, float wd, float bc2_sqrt, float gscale) {
   const long long n4 = count / 4;

@@ -10,6 +10,10 @@ One fused HIP pass computes sigmoid, the three per-(n,c) sums, the loss and d(lo
 The cross-entropy leg of the same look-up (script_utils.py:61-77 tries unet3d.losses, torch.nn, monai.losses in that order:
 torch.nn.BCEWithLogitsLoss / CrossEntropyLoss, monai.losses.DiceCELoss) is one more fused pass (mi355_ce_fwd_bwd) that adds
 its value and gradient to the Dice term's.
+
+HipFocalLoss / HipDiceFocalLoss / HipTverskyLoss (monai.losses.FocalLoss, DiceFocalLoss, TverskyLoss: the small-lesion losses) follow the
+same pattern: the focal term is one fused pass (mi355_focal_fwd_bwd, csrc/focal.hip) that lands on top of a Dice term the way the CE pass
+does; Tversky runs on the extended Dice's passes with its own finaliser (mi355_tversky_forward / mi355_tversky_backward).
 """
 import torch
 import torch.nn as nn
@@ -325,3 +329,220 @@ class HipCrossEntropyLoss(_CEBase):
                 raise ValueError(f"HipCrossEntropyLoss: class-index target outside [0, {input.shape[1]}) (min {lo}, max {hi}): "
                                  "ignore_index / out-of-range labels are not implemented")
         return super().forward(input, target)
+
+
+# ---- focal / Dice + focal / Tversky (monai.losses.FocalLoss, DiceFocalLoss, TverskyLoss) ---------------------------------------------
+def _reduction(reduction, allowed, who):
+    reduction = str(getattr(reduction, "value", reduction)).lower()
+    if reduction not in ("mean", "sum", "none"):
+        raise ValueError(f'Unsupported reduction: {reduction}, available options are ["mean", "sum", "none"].')
+    if reduction not in allowed:
+        raise NotImplementedError(f"{who} does not implement: reduction={reduction!r}")
+    return reduction
+
+
+def _check_activation(who, sigmoid, softmax, other_act):
+    if other_act is not None and not callable(other_act):
+        raise TypeError(f"other_act must be None or callable but is {type(other_act).__name__}.")
+    if int(bool(sigmoid)) + int(bool(softmax)) + int(other_act is not None) > 1:
+        raise ValueError("Incompatible values: more than 1 of [sigmoid=True, softmax=True, other_act is not None].")
+    if other_act is not None:
+        raise NotImplementedError(f"{who} does not implement: other_act (a Python callable cannot run inside the fused kernels)")
+
+
+def _check_focal(gamma, alpha):
+    gamma = float(gamma)
+    if not gamma >= 0.0 or gamma == float("inf"):
+        raise ValueError(f"gamma should be a finite number no less than 0 but is {gamma}.")
+    if alpha is not None:
+        alpha = float(alpha)
+        if not 0.0 <= alpha <= 1.0:
+            raise ValueError(f"alpha should be in [0, 1] but is {alpha}.")
+    return gamma, alpha
+
+
+class _ClassWeighted(nn.Module):
+    """`weight` of the MONAI losses: a buffer whose sign is read on the host once per value (HipDiceLoss._check_weight_sign), expanded /
+    length-checked against the counted classes at every forward."""
+    _check_weight_sign = HipDiceLoss._check_weight_sign
+
+    def _init_weight(self, weight):
+        self.register_buffer("class_weight", torch.as_tensor(weight, dtype=torch.float32) if weight is not None else None)
+        self._weight_checked = None
+        self._weight_negative = False
+        self._check_weight_sign()
+        if self._weight_negative:
+            raise ValueError("the value/values of the `weight` should be no less than 0.")
+
+    def _counted_weight(self, ce):
+        cw = self.class_weight
+        if cw is None:
+            return None
+        if cw.ndim == 0:
+            cw = cw.repeat(ce)
+        elif cw.shape[0] != ce:
+            raise ValueError("the length of the `weight` sequence should be the same as the number of classes. "
+                             "If `include_background=False`, the weight should not include the background category class 0.")
+        self._check_weight_sign()
+        if self._weight_negative:
+            raise ValueError("the value/values of the `weight` should be no less than 0.")
+        return cw
+
+    def _prepare(self, input, target, onehot):
+        """the checks every forward of this family starts with -> (counted classes, target in a type the kernels read)"""
+        if input.device.type != "cuda" and self._be is None:
+            raise RuntimeError(f"{type(self).__name__} runs on an MI355X only (no CPU fallback)")
+        c = input.shape[1]
+        if c > 16:
+            raise NotImplementedError("more than 16 classes")
+        if not self.include_background and c == 1:
+            raise ValueError("single channel prediction, `include_background=False` ignored is not supported: pass include_background=True")
+        if onehot and c > 1:                                # MONAI: "single channel prediction, `to_onehot_y=True` ignored."
+            if target.shape[0] != input.shape[0] or target.shape[1] != 1 or target.shape[2:] != input.shape[2:]:
+                raise AssertionError("labels should have a channel with length equal to one.")             # monai.networks.one_hot
+            target = target.to(torch.int32)
+        else:
+            if target.shape != input.shape:
+                raise AssertionError(f"ground truth has different shape ({tuple(target.shape)}) from input ({tuple(input.shape)})")
+            if target.dtype not in (torch.uint8, torch.float32):
+                target = target.to(torch.float32)
+        return c - (0 if self.include_background else 1), target
+
+
+class _DiceFocalFunction(torch.autograd.Function):
+    """loss = lambda_dice * Dice + lambda_focal * Focal (lambda_dice = 0: the focal term alone), value and d/dlogits from the fused HIP
+    passes: the focal pass accumulates onto the Dice term's value and gradient the way the CE pass of _CEFunction does."""
+    @staticmethod
+    def forward(ctx, logits, target, mod, cw):
+        be = mod._be or _ops.default_backend(logits.device)
+        want = ctx.needs_input_grad[0]
+        logits, target = logits.contiguous(), target.contiguous()
+        c = logits.shape[1]
+        if cw is not None:
+            cw = cw.to(device=logits.device, dtype=torch.float32).contiguous()
+        loss = dlogits = None
+        if mod.lambda_dice != 0.0:
+            if target.dtype == torch.int32:                  # a label map is expanded once, both terms use the expansion
+                target = _onehot_u8(be, target, c)
+            dice_cw = cw if c - (0 if mod.include_background else 1) != 1 else None       # MONAI's Dice weights more than one class only
+            if not (mod.softmax or mod.jaccard or dice_cw is not None or mod.reduction == "sum"):
+                loss, dlogits = be.dice(logits, target, sigmoid=mod.sigmoid, batch=mod.batch, squared_pred=mod.squared_pred,
+                                        smooth_nr=mod.smooth_nr, smooth_dr=mod.smooth_dr, want_grad=want, grad_scale=mod.lambda_dice,
+                                        include_background=mod.include_background)
+            else:
+                act = "softmax" if mod.softmax and c > 1 else ("sigmoid" if mod.sigmoid else None)
+                loss, state = be.dice_ex_forward(logits, target, activation=act, batch=mod.batch, squared_pred=mod.squared_pred,
+                                                 include_background=mod.include_background, jaccard=mod.jaccard, reduction=mod.reduction,
+                                                 smooth_nr=mod.smooth_nr, smooth_dr=mod.smooth_dr, class_weight=dice_cw)
+                if want:
+                    dlogits = be.dice_ex_backward(logits, target, state, torch.full((1,), mod.lambda_dice, dtype=torch.float32,
+                                                                                    device=logits.device))
+            loss.mul_(mod.lambda_dice)
+        if mod.lambda_focal != 0.0:
+            loss, dlogits = be.focal(logits, target, mode="softmax" if mod.focal_softmax else "sigmoid", gamma=mod.gamma, alpha=mod.alpha,
+                                     include_background=mod.include_background, reduction=mod.reduction, class_weight=cw,
+                                     weight=mod.lambda_focal, loss=loss, dlogits=dlogits if want else None, want_grad=want)
+        ctx.dlogits = dlogits
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        return _scaled(ctx, g), None, None, None
+
+
+class HipFocalLoss(_ClassWeighted):
+    """monai.losses.FocalLoss: one fused pass (value + gradient, mi355_focal_fwd_bwd). Sigmoid form by default, the softmax form with
+    use_softmax=True and more than one counted channel; `alpha` balances positives against negatives (sigmoid) or foreground against
+    background (softmax: 1 - alpha on channel 0, alpha elsewhere); `weight`: one factor per counted class; include_background=False drops
+    channel 0 before the activation; to_onehot_y takes a class-index target [N, 1, ...] (read as indices, no one-hot tensor is made).
+    reduction "mean" | "sum" (MONAI's: the sum over (n, c) of the spatial mean); "none" raises."""
+    lambda_dice, lambda_focal = 0.0, 1.0
+
+    def __init__(self, include_background=True, to_onehot_y=False, gamma=2.0, alpha=None, weight=None, reduction="mean", use_softmax=False):
+        super().__init__()
+        self.reduction = _reduction(reduction, ("mean", "sum"), type(self).__name__)
+        self.gamma, self.alpha = _check_focal(gamma, alpha)
+        self.include_background, self.to_onehot_y, self.focal_softmax = bool(include_background), bool(to_onehot_y), bool(use_softmax)
+        self._init_weight(weight)
+        self._be = None
+
+    def forward(self, input, target):
+        ce, target = self._prepare(input, target, self.to_onehot_y)
+        return _DiceFocalFunction.apply(input.float(), target, self, self._counted_weight(ce))
+
+
+class HipDiceFocalLoss(_ClassWeighted):
+    """monai.losses.DiceFocalLoss: lambda_dice * DiceLoss(...) + lambda_focal * FocalLoss(...). sigmoid / softmax / squared_pred / jaccard /
+    batch / smooth_* configure the Dice term; the focal term sees the raw logits, in the softmax form iff softmax=True; gamma / alpha
+    configure it. include_background, to_onehot_y (the label map is expanded once, both terms read the expansion), `weight` (class
+    weights) and reduction "mean" | "sum" apply to both. Not implemented (raise): other_act, reduction "none"."""
+    def __init__(self, include_background=True, to_onehot_y=False, sigmoid=False, softmax=False, other_act=None, squared_pred=False,
+                 jaccard=False, reduction="mean", smooth_nr=1e-5, smooth_dr=1e-5, batch=False, gamma=2.0, weight=None, lambda_dice=1.0,
+                 lambda_focal=1.0, alpha=None):
+        super().__init__()
+        _check_activation(type(self).__name__, sigmoid, softmax, other_act)
+        self.reduction = _reduction(reduction, ("mean", "sum"), type(self).__name__)
+        self.gamma, self.alpha = _check_focal(gamma, alpha)
+        self.lambda_dice, self.lambda_focal = float(lambda_dice), float(lambda_focal)
+        if self.lambda_dice < 0.0 or self.lambda_focal < 0.0:
+            raise ValueError("lambda_dice and lambda_focal should be no less than 0.0.")      # MONAI's checks, same messages
+        if self.lambda_dice == 0.0 and self.lambda_focal == 0.0:
+            raise ValueError("HipDiceFocalLoss: lambda_dice and lambda_focal are both 0 -- the loss would be identically zero")
+        self.sigmoid, self.softmax, self.to_onehot_y = bool(sigmoid), bool(softmax), bool(to_onehot_y)
+        self.squared_pred, self.jaccard, self.batch = bool(squared_pred), bool(jaccard), bool(batch)
+        self.smooth_nr, self.smooth_dr = float(smooth_nr), float(smooth_dr)
+        self.include_background = bool(include_background)
+        self.focal_softmax = self.softmax
+        self._init_weight(weight)
+        self._be = None
+
+    def forward(self, input, target):
+        ce, target = self._prepare(input, target, self.to_onehot_y)
+        return _DiceFocalFunction.apply(input.float(), target, self, self._counted_weight(ce))
+
+
+class _TverskyFunction(torch.autograd.Function):
+    """forward = the Dice sums + the Tversky finalisation, backward = one pass that applies the upstream gradient of every term"""
+    @staticmethod
+    def forward(ctx, logits, target, mod, activation):
+        be = mod._be or _ops.default_backend(logits.device)
+        logits, target = logits.contiguous(), target.contiguous()
+        loss, state = be.tversky_forward(logits, target, activation=activation, alpha=mod.alpha, beta=mod.beta, batch=mod.batch,
+                                         include_background=mod.include_background, reduction=mod.reduction, smooth_nr=mod.smooth_nr,
+                                         smooth_dr=mod.smooth_dr)
+        ctx.saved = (be, logits, target, state)
+        if mod.reduction != "none":
+            return loss.reshape(())
+        ce = logits.shape[1] - (0 if mod.include_background else 1)
+        lead = [ce] if mod.batch else [logits.shape[0], ce]
+        return loss.reshape(lead + [1] * (logits.dim() - 2))
+
+    @staticmethod
+    def backward(ctx, g):
+        if ctx.saved is None:
+            raise RuntimeError("loss backward called a second time: its saved tensors are released by the first backward")
+        be, logits, target, state = ctx.saved
+        ctx.saved = None
+        return be.tversky_backward(logits, target, state, g), None, None, None
+
+
+class HipTverskyLoss(_ClassWeighted):
+    """monai.losses.TverskyLoss: 1 - (tp + smooth_nr) / (tp + alpha fp + beta fn + smooth_dr) per (n, c) (per c with batch) on the sums of
+    the extended Dice passes; activation, to_onehot_y, include_background, batch and reduction "mean" | "sum" | "none" as in HipDiceLoss."""
+    def __init__(self, include_background=True, to_onehot_y=False, sigmoid=False, softmax=False, other_act=None, alpha=0.5, beta=0.5,
+                 reduction="mean", smooth_nr=1e-5, smooth_dr=1e-5, batch=False):
+        super().__init__()
+        _check_activation(type(self).__name__, sigmoid, softmax, other_act)
+        self.reduction = _reduction(reduction, ("mean", "sum", "none"), type(self).__name__)
+        self.alpha, self.beta = float(alpha), float(beta)
+        if self.alpha != self.alpha or self.beta != self.beta:
+            raise ValueError("alpha and beta should be numbers.")
+        self.sigmoid, self.softmax, self.to_onehot_y, self.batch = bool(sigmoid), bool(softmax), bool(to_onehot_y), bool(batch)
+        self.smooth_nr, self.smooth_dr = float(smooth_nr), float(smooth_dr)
+        self.include_background = bool(include_background)
+        self._be = None
+
+    def forward(self, input, target):
+        _, target = self._prepare(input, target, self.to_onehot_y)
+        softmax = self.softmax and input.shape[1] > 1        # MONAI: "single channel prediction, `softmax=True` ignored."
+        return _TverskyFunction.apply(input.float(), target, self, "softmax" if softmax else ("sigmoid" if self.sigmoid else None))

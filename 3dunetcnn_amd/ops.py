@@ -15,7 +15,7 @@ import torch
 
 from . import _lib
 from ._lib import (IN_AFFINE_ACT, IN_PLAIN, IN_S2D, IN_ZERO_INSERT, OUT_D2S, OUT_PLAIN, PREC_F32, PRECISIONS, W_OIDHW4,  # noqa: F401
-                   W_PACKED, W_PACKED_F32_NARROW, MiAct, MiConvDesc, MiDiceOpts, MiGnBwdFuse, check)
+                   W_PACKED, W_PACKED_F32_NARROW, MiAct, MiConvDesc, MiDiceOpts, MiFocalOpts, MiGnBwdFuse, MiTverskyOpts, check)
 
 
 # MI355_HOST_CACHES=0: the per-call forms of round 4 (descriptors, the Winograd routing query, the engine's parameter list and gradient
@@ -944,6 +944,61 @@ class Backend:
                                         {"softmax": 0, "bce": 1}[mode], float(weight), loss.data_ptr(), int(acc_l), _p(dlogits), int(acc_g),
                                         float(grad_scale), ws.data_ptr(), ws.numel() * 4, self.stream()), "ce_fwd_bwd")
         return loss, dlogits
+
+    def focal(self, logits, target, mode="sigmoid", gamma=2.0, alpha=None, include_background=True, reduction="mean", class_weight=None,
+              weight=1.0, loss=None, dlogits=None, want_grad=True, grad_scale=1.0):
+        """Focal loss (mi355_focal_fwd_bwd). mode "sigmoid" | "softmax"; target: the logits' shape (uint8 / fp32) or an int32 label map
+        [n, 1, ...] / [n, ...]; reduction "mean" | "sum" (sum over (n, c) of the spatial mean); class_weight: device fp32, one factor per
+        counted class. `loss` / `dlogits` given: weight x the value / gradient is ADDED to them (on top of a Dice term); else fresh tensors."""
+        assert logits.is_contiguous() and target.is_contiguous() and logits.dtype == torch.float32
+        n, c = logits.shape[0], logits.shape[1]
+        vox = logits[0, 0].numel()
+        assert (target.dtype == torch.int32 and target.numel() == n * vox) or (target.dtype in (torch.uint8, torch.float32) and target.shape == logits.shape)
+        assert class_weight is None or (class_weight.dtype == torch.float32 and class_weight.is_contiguous()
+                                        and class_weight.numel() == c - (0 if include_background else 1))
+        kind = 2 if target.dtype == torch.int32 else (1 if target.dtype == torch.uint8 else 0)
+        o = MiFocalOpts({"sigmoid": 0, "softmax": 1}[mode], kind, int(include_background), {"mean": 0, "sum": 1}[reduction],
+                        int(alpha is not None), float(gamma), float(alpha if alpha is not None else 0.0), _p(class_weight))
+        acc_l, acc_g = loss is not None, dlogits is not None
+        if loss is None:
+            loss = torch.empty(1, dtype=torch.float32, device=self.device)
+        if dlogits is None and want_grad:
+            dlogits = torch.empty_like(logits)
+        ws = self.ws(_lib.FOCAL_SCRATCH_BYTES)
+        check(self.lib.mi355_focal_fwd_bwd(ctypes.byref(o), logits.data_ptr(), target.data_ptr(), n, c, vox, float(weight), loss.data_ptr(),
+                                           int(acc_l), _p(dlogits), int(acc_g), float(grad_scale), ws.data_ptr(), ws.numel() * 4,
+                                           self.stream()), "focal_fwd_bwd")
+        return loss, dlogits
+
+    def tversky_forward(self, logits, target, activation="sigmoid", alpha=0.5, beta=0.5, batch=False, include_background=True,
+                        reduction="mean", smooth_nr=1e-5, smooth_dr=1e-5):
+        """monai TverskyLoss on the extended Dice passes. target as in dice_ex_forward. Returns (loss values [1] or one per term, state for
+        tversky_backward)."""
+        assert logits.is_contiguous() and target.is_contiguous() and logits.dtype == torch.float32
+        n, c = logits.shape[0], logits.shape[1]
+        vox = logits[0, 0].numel()
+        assert (target.dtype == torch.int32 and target.numel() == n * vox) or (target.dtype in (torch.uint8, torch.float32) and target.shape == logits.shape)
+        ce = c - (0 if include_background else 1)
+        terms = (ce if batch else n * ce) if reduction == "none" else 1
+        loss = torch.empty(terms, dtype=torch.float32, device=self.device)
+        kind = 2 if target.dtype == torch.int32 else (1 if target.dtype == torch.uint8 else 0)
+        o = MiTverskyOpts(self.DICE_ACT[activation], kind, int(batch), int(include_background), self.DICE_REDUCE[reduction], float(alpha),
+                          float(beta), float(smooth_nr), float(smooth_dr))
+        ws = torch.empty(self.lib.mi355_dice_workspace(n, c, vox) // 4, dtype=torch.float32, device=self.device)   # kept for backward
+        check(self.lib.mi355_tversky_forward(ctypes.byref(o), logits.data_ptr(), target.data_ptr(), n, c, vox, loss.data_ptr(), ws.data_ptr(),
+                                             ws.numel() * 4, self.stream()), "tversky_forward")
+        return loss, (o, ws)
+
+    def tversky_backward(self, logits, target, state, upstream):
+        """d(sum_t upstream[t] * loss[t]) / d(logits); upstream: fp32 tensor with one value per loss value."""
+        o, ws = state
+        n, c = logits.shape[0], logits.shape[1]
+        vox = logits[0, 0].numel()
+        dlogits = torch.empty_like(logits)
+        upstream = upstream.reshape(-1).contiguous().float()
+        check(self.lib.mi355_tversky_backward(ctypes.byref(o), logits.data_ptr(), target.data_ptr(), n, c, vox, upstream.data_ptr(),
+                                              upstream.numel(), dlogits.data_ptr(), ws.data_ptr(), self.stream()), "tversky_backward")
+        return dlogits
 
     def adam_step(self, p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0):
         check(self.lib.mi355_adam_step(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), lr, beta1, beta2, eps,

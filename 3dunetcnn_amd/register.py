@@ -16,7 +16,8 @@ import torch
 
 def register(replace=False):
     from .dynunet import HipDynUNet
-    from .losses import HipBCEWithLogitsLoss, HipCrossEntropyLoss, HipDiceCELoss, HipDiceLoss, HipGeneralizedDiceLoss
+    from .losses import (HipBCEWithLogitsLoss, HipCrossEntropyLoss, HipDiceCELoss, HipDiceFocalLoss, HipDiceLoss, HipFocalLoss,
+                         HipGeneralizedDiceLoss, HipTverskyLoss)
     from .optim import HipAdam
     from .unet import HipAutocastUNet, HipAutoImplantUNet, HipUNet3D
     done = {}
@@ -39,7 +40,8 @@ def register(replace=False):
         losses = importlib.import_module("unet3d.losses")
         hip_losses = {"HipDiceLoss": HipDiceLoss, "HipDiceCELoss": HipDiceCELoss, "HipGeneralizedDiceLoss": HipGeneralizedDiceLoss,
                       "HipBCEWithLogitsLoss": HipBCEWithLogitsLoss,
-                      "HipCrossEntropyLoss": HipCrossEntropyLoss}
+                      "HipCrossEntropyLoss": HipCrossEntropyLoss, "HipFocalLoss": HipFocalLoss, "HipDiceFocalLoss": HipDiceFocalLoss,
+                      "HipTverskyLoss": HipTverskyLoss}
         for name, cls in hip_losses.items():
             setattr(losses, name, cls)
         done["losses"] = list(hip_losses)

@@ -459,6 +459,57 @@ int mi355_ce_fwd_bwd(const float* logits, const void* target, int32_t target_is_
                      float weight, float* loss, int32_t accumulate_loss, float* dlogits, int32_t accumulate_grad, float grad_scale,
                      void* ws, size_t ws_bytes, void* stream);
 
+/* ---- focal loss ------------------------------------------------------------------------------ */
+/* monai.losses.FocalLoss and the focal term of monai.losses.DiceFocalLoss (any monai.losses name is a legal configuration of the
+ * reference: scripts/script_utils.py:61-77), one streaming pass over the logits: the value and, when dlogits != NULL, the gradient.
+ * MONAI is not vendored; these formulas are the contract. w_c: class_weight (1 when NULL), g: gamma, y in [0, 1].
+ *   MI355_FOCAL_SIGMOID, per counted element:
+ *        B = max(z, 0) - z y + log1p(exp(-|z|))              (binary cross-entropy with logits)
+ *        u = -z (2y - 1);  M = exp(g logsigmoid(u));  a = alpha y + (1 - alpha)(1 - y) with has_alpha, else 1
+ *        l = w_c a B M;    dl/dz = w_c a M [ (sigmoid(z) - y) - g B sigmoid(-u) (2y - 1) ]
+ *   MI355_FOCAL_SOFTMAX, per voxel (with a single counted channel the sigmoid form is used instead):
+ *        ls = log_softmax(z) over the COUNTED channels;  l_c = -w_c a_c y_c (1 - exp(ls_c))^g ls_c
+ *        a_c = 1 - alpha for channel 0 (the background) and alpha for every other channel with has_alpha, else 1
+ *        the gradient flows through the softmax to every counted channel; (1 - p)^g and its derivative are 0 at p == 1 for g > 0.
+ *   include_background == 0: channel 0 is dropped from logits and target BEFORE the activation (the softmax runs over channels
+ *        1 .. c-1) and receives a zero gradient from this term (left untouched when accumulate_grad != 0).
+ *   target_kind: MI355_DICE_TARGET_F32 / _U8 (the logits' shape) or _LABELS (int32 [n][voxels], y_c = label == c).
+ *   reduction: MI355_DICE_REDUCE_MEAN = sum of l over the counted elements / (n * counted channels * voxels);
+ *        MI355_DICE_REDUCE_SUM = sum over (n, c) of the spatial mean = sum of l / voxels (the scale of the Dice term's "sum").
+ *   class_weight: device pointer, one factor per COUNTED class, or NULL.
+ * loss[0] = weight * focal (+= with accumulate_loss, e.g. after a Dice term); dlogits receives weight * grad_scale * d focal / d logits,
+ * ADDED to its contents with accumulate_grad. Offsets are 64-bit (n * c * voxels may exceed 2^31). c <= 16 (else MI355_EUNSUPPORTED).
+ * MI355_EINVAL: a null pointer, n / c / voxels <= 0, mode / target_kind / reduction out of range, gamma negative or not finite, alpha
+ * outside [0, 1], include_background == 0 with c < 2. ws: MI355_FOCAL_SCRATCH_BYTES bytes (one partial per block, summed in double by a
+ * one-block finaliser in index order: no floating-point atomics, the same bits on every call). Two launches. */
+#define MI355_FOCAL_SIGMOID 0
+#define MI355_FOCAL_SOFTMAX 1
+#define MI355_FOCAL_SCRATCH_BYTES 4096
+typedef struct mi355_focal_opts {
+  int32_t mode, target_kind, include_background, reduction, has_alpha;
+  float gamma, alpha;
+  const float* class_weight;
+} mi355_focal_opts;
+int mi355_focal_fwd_bwd(const mi355_focal_opts* opts, const float* logits, const void* target, int32_t n, int32_t c, int64_t voxels,
+                        float weight, float* loss, int32_t accumulate_loss, float* dlogits, int32_t accumulate_grad, float grad_scale,
+                        void* ws, size_t ws_bytes, void* stream);
+
+/* ---- Tversky loss ---------------------------------------------------------------------------- */
+/* monai.losses.TverskyLoss on the passes of the extended Dice: per (n, c) -- per c with batch -- with p = activation(logits),
+ *   tp = sum p y, fp = sum p (1 - y), fn = sum (1 - p) y;  f = 1 - (tp + smooth_nr) / (tp + alpha fp + beta fn + smooth_dr)
+ * i.e. with the Dice sums I, P, Y: denominator D = (1 - alpha - beta) I + alpha P + beta Y + smooth_dr and
+ *   df/dp = -[ y D - (I + smooth_nr) ((1 - alpha - beta) y + alpha) ] / D^2      (linear in y: the pair the Dice gradient pass consumes).
+ * activation, target_kind, include_background, batch, reduction, loss, upstream: as mi355_dice_ex_forward / mi355_dice_ex_backward.
+ * ws: mi355_dice_workspace(n, c, voxels) bytes, written by forward and read by backward. alpha / beta: any number (NaN: MI355_EINVAL). */
+typedef struct mi355_tversky_opts {
+  int32_t activation, target_kind, batch, include_background, reduction;
+  float alpha, beta, smooth_nr, smooth_dr;
+} mi355_tversky_opts;
+int mi355_tversky_forward(const mi355_tversky_opts* opts, const float* logits, const void* target, int32_t n, int32_t c, int64_t voxels,
+                          float* loss, void* ws, size_t ws_bytes, void* stream);
+int mi355_tversky_backward(const mi355_tversky_opts* opts, const float* logits, const void* target, int32_t n, int32_t c, int64_t voxels,
+                           const float* upstream, int32_t n_upstream, float* dlogits, const void* ws, void* stream);
+
 /* ---- optimizer -------------------------------------------------------------------------------- */
 /* torch.optim.Adam(lr, betas, eps, weight_decay=0, amsgrad=False).step() (script_utils.py:80-81) over one flat
  * parameter buffer; grad is multiplied by grad_scale first (1/world_size after the RCCL sum). step is 1-based.
