@@ -1,6 +1,6 @@
 // Focal loss (monai.losses.FocalLoss, and the focal term of DiceFocalLoss): value and d/dlogits in one streaming pass over the logits,
-// on the pattern of mi355_ce_fwd_bwd (loss_optim.hip): one partial per block into the workspace, a single-block finaliser that sums
-// them in double in index order (no floating-point atomics: two calls on the same inputs give the same bits), `weight` /
+// on the pattern of mi355_ce_fwd_bwd (loss_optim.hip): one partial per block into the workspace, a single-block finaliser
+// (loss_finalize_kernel, loss_common.h) that sums them in double in index order (no floating-point atomics: two calls on the same inputs give the same bits), `weight` /
 // `accumulate_loss` / `accumulate_grad` / `grad_scale` so that the term lands on top of a Dice term the way the CE term does.
 //
 // Formulas (include/mi355_unet3d.h states them in full). w_c: class weight, a: the alpha factor, g: gamma.
@@ -12,6 +12,7 @@
 // for every g > 0 (the limit), never 0 * inf.
 #include "gfx950_dialect.h"
 #include "../../include/mi355_unet3d.h"
+#include "loss_common.h"
 
 #define FOCAL_BLOCKS 1024
 #define FOCAL_MAX_C 16
@@ -23,12 +24,6 @@ struct FocalArgs {
   float gamma, alpha, gscale;
   const float* class_w;
 };
-
-__device__ __forceinline__ float focal_y(const void* target, int kind, long long V, int C, long long n, int c, long long v) {
-  if (kind == MI355_DICE_TARGET_LABELS) return ((const int*)target)[(size_t)n * V + v] == c ? 1.f : 0.f;
-  const size_t i = ((size_t)n * C + c) * V + v;
-  return kind == MI355_DICE_TARGET_U8 ? (float)((const unsigned char*)target)[i] : ((const float*)target)[i];
-}
 
 // e = exp(-|x|) given: log(1 + exp(-|x|)) and sigmoid(x) without a second exponential
 __device__ __forceinline__ float sigmoid_from(float x, float e) { const float r = 1.f / (1.f + e); return x >= 0.f ? r : e * r; }
@@ -47,7 +42,7 @@ __global__ void focal_kernel(const float* z, const void* target, FocalArgs a, fl
     if constexpr (!SOFTMAX) {
       for (int c = c0; c < C; ++c) {
         const float zz = z[base + (size_t)c * V];
-        const float y = focal_y(target, a.kind, V, C, n, c, v);
+        const float y = loss_target(target, a.kind, V, C, n, c, v);
         const float s = 2.f * y - 1.f, u = -zz * s;
         const float ez = expf(-fabsf(zz)), l1z = log1pf(ez);
         float eu = ez, l1u = l1z;                                  // a hard target (y = 0 or 1): |u| == |z|, the same two values
@@ -79,7 +74,7 @@ __global__ void focal_kernel(const float* z, const void* target, FocalArgs a, fl
 #pragma unroll
       for (int j = 0; j < FOCAL_MAX_C; ++j)
         if (j < Ce) {
-          const float y = focal_y(target, a.kind, V, C, n, c0 + j, v);
+          const float y = loss_target(target, a.kind, V, C, n, c0 + j, v);
           const float ls = zc[j] - lse;
           const float q = -expm1f(ls);                             // 1 - p, exact 0 only where ls == 0
           float k = (a.class_w ? a.class_w[j] : 1.f) * y;
@@ -104,29 +99,8 @@ __global__ void focal_kernel(const float* z, const void* target, FocalArgs a, fl
       }
     }
   }
-  red[threadIdx.x] = local;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
+  block_sum_256(red, local);
   if (threadIdx.x == 0) part[blockIdx.x] = red[0];
-}
-
-__global__ void focal_finalize_kernel(const float* part, int B, double inv_count, float weight, float* loss, int accumulate) {
-  __shared__ double red[256];
-  double s = 0.0;
-  for (int b = threadIdx.x; b < B; b += blockDim.x) s += (double)part[b];
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int k = 128; k > 0; k >>= 1) {
-    if ((int)threadIdx.x < k) red[threadIdx.x] += red[threadIdx.x + k];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    const float v = (float)(red[0] * inv_count) * weight;
-    loss[0] = accumulate ? loss[0] + v : v;
-  }
 }
 
 extern "C" int mi355_focal_fwd_bwd(const mi355_focal_opts* o, const float* logits, const void* target, int32_t n, int32_t c, int64_t voxels,
@@ -155,6 +129,6 @@ extern "C" int mi355_focal_fwd_bwd(const mi355_focal_opts* o, const float* logit
   else
     LAUNCH((focal_kernel<0>), dim3((unsigned)g), dim3(256), 0, stream, logits, target, a, dlogits, (float*)ws);
   int rc = LAUNCH_CHECK(); if (rc) return rc;
-  LAUNCH(focal_finalize_kernel, dim3(1), dim3(256), 0, stream, (const float*)ws, (int)g, 1.0 / count, weight, loss, accumulate_loss);
+  LAUNCH(loss_finalize_kernel, dim3(1), dim3(256), 0, stream, (const float*)ws, (int)g, 1.0 / count, weight, loss, accumulate_loss);
   return LAUNCH_CHECK();
 }

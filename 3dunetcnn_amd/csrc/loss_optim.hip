@@ -8,6 +8,7 @@
 // Adam: torch.optim.Adam defaults (script_utils.py:80-81), single flat parameter buffer.
 #include "gfx950_dialect.h"
 #include "../../include/mi355_unet3d.h"
+#include "loss_common.h"
 
 #define DICE_MAX_BLOCKS 128
 
@@ -55,12 +56,9 @@ __global__ void dice_partial_kernel(const float* logits, const void* target, int
 // jaccard (variant 0): denominator 2 (D - I) instead of D. class_w: one factor per counted class (or NULL). reduction 0 mean / 1 sum /
 // 2 none: with "none" loss[] receives one value per term (n-major, counted classes only; one row with batch) and the coefficients are those
 // of sum (the caller applies the upstream gradient of every term).
-__global__ void dice_finalize_kernel(const float* ws, int B, int N, int C, int batch, float snr, float sdr, float grad_scale,
-                                     int variant, int c0, float* stats, float* coef, float* loss,
-                                     int jaccard, const float* class_w, int reduction) {
-  __shared__ double sums[3 * 1024];
-  __shared__ double fsum[256];
-  const int NC = N * C;
+// prologue of the Dice and Tversky finalisers: block partials [NC][B][3] -> the three sums per (n, c), in double (sums, shared) and in
+// float (stats, in the workspace)
+__device__ __forceinline__ void dice_load_sums(const float* ws, int B, int NC, double* sums, float* stats) {
   for (int i = threadIdx.x; i < NC; i += blockDim.x) {
     double a = 0.0, b = 0.0, c = 0.0;
     for (int k = 0; k < B; ++k) { const float* p = ws + ((size_t)i * B + k) * 3; a += (double)p[0]; b += (double)p[1]; c += (double)p[2]; }
@@ -68,6 +66,20 @@ __global__ void dice_finalize_kernel(const float* ws, int B, int N, int C, int b
     stats[3 * i] = (float)a; stats[3 * i + 1] = (float)b; stats[3 * i + 2] = (float)c;
   }
   __syncthreads();
+}
+// their epilogue: the block sum of every thread's share f of the reduced loss -> loss[0] (not with reduction "none": loss[] holds the terms)
+__device__ __forceinline__ void dice_store_loss(double* fsum, double f, bool reduced, float* loss) {
+  block_sum_256(fsum, f);
+  if (threadIdx.x == 0 && reduced) loss[0] = (float)fsum[0];
+}
+
+__global__ void dice_finalize_kernel(const float* ws, int B, int N, int C, int batch, float snr, float sdr, float grad_scale,
+                                     int variant, int c0, float* stats, float* coef, float* loss,
+                                     int jaccard, const float* class_w, int reduction) {
+  __shared__ double sums[3 * 1024];
+  __shared__ double fsum[256];
+  const int NC = N * C;
+  dice_load_sums(ws, B, NC, sums, stats);
   double f = 0.0;
   const int Ce = C - c0;                                  // channels that count
   if (variant == 0) {
@@ -117,10 +129,7 @@ __global__ void dice_finalize_kernel(const float* ws, int B, int N, int C, int b
       if (c == c0 && (!batch || n == 0)) f += (1.0 - numer / denom) / K;
     }
   }
-  fsum[threadIdx.x] = f;
-  __syncthreads();
-  for (int s = blockDim.x / 2; s > 0; s >>= 1) { if ((int)threadIdx.x < s) fsum[threadIdx.x] += fsum[threadIdx.x + s]; __syncthreads(); }
-  if (threadIdx.x == 0 && !(variant == 0 && reduction == 2)) loss[0] = (float)fsum[0];
+  dice_store_loss(fsum, f, !(variant == 0 && reduction == 2), loss);
 }
 
 __global__ void dice_grad_kernel(const float* logits, const void* target, int target_u8, long long V, int NC, int sigmoid, int squared,
@@ -140,11 +149,6 @@ __global__ void dice_grad_kernel(const float* logits, const void* target, int ta
 
 // ---- extended Dice (monai DiceLoss options beyond the shipped configuration: softmax, to_onehot_y, jaccard, weight, reduction) ----
 #define DICE_MAX_C 16
-__device__ __forceinline__ float dice_y(const void* target, int kind, long long V, int C, int n, int c, long long v) {
-  if (kind == MI355_DICE_TARGET_LABELS) return ((const int*)target)[(size_t)n * V + v] == c ? 1.f : 0.f;
-  const size_t i = ((size_t)n * C + c) * V + v;
-  return kind == MI355_DICE_TARGET_U8 ? (float)((const unsigned char*)target)[i] : ((const float*)target)[i];
-}
 // p[c] = act(z[c]) for the C channels of one voxel
 __device__ __forceinline__ void dice_probs(const float* z, long long V, int C, int act, long long v, float (&p)[DICE_MAX_C]) {
   if (act == MI355_DICE_ACT_SOFTMAX) {
@@ -172,7 +176,7 @@ __global__ void dice_ex_partial_kernel(const float* logits, const void* target, 
     float p[DICE_MAX_C];
     dice_probs(z, V, C, act, v, p);
     for (int c = 0; c < C; ++c) {
-      const float y = dice_y(target, kind, V, C, n, c, v);
+      const float y = loss_target(target, kind, V, C, n, c, v);
       sI[c] += p[c] * y;
       sP[c] += squared ? p[c] * p[c] : p[c];
       sY[c] += squared ? y * y : y;
@@ -180,13 +184,8 @@ __global__ void dice_ex_partial_kernel(const float* logits, const void* target, 
   }
   for (int c = 0; c < C; ++c)
     for (int k = 0; k < 3; ++k) {
-      __syncthreads();
-      red[threadIdx.x] = k == 0 ? sI[c] : k == 1 ? sP[c] : sY[c];
-      __syncthreads();
-      for (int s = blockDim.x / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-      }
+      __syncthreads();                                         // red is reused: thread 0 has read the previous sum
+      block_sum_256(red, k == 0 ? sI[c] : k == 1 ? sP[c] : sY[c]);
       if (threadIdx.x == 0) ws[(((size_t)n * C + c) * B + blk) * 3 + k] = red[0];
     }
 }
@@ -207,7 +206,7 @@ __global__ void dice_ex_grad_kernel(const float* logits, const void* target, int
     for (int c = 0; c < C; ++c) {
       float up = 1.f;
       if (upstream) up = n_up == 1 ? upstream[0] : (c >= c0 ? upstream[batch ? c - c0 : n * Ce + c - c0] : 0.f);
-      const float y = dice_y(target, kind, V, C, n, c, v);
+      const float y = loss_target(target, kind, V, C, n, c, v);
       g[c] = up * (-coef[2 * (n * C + c)] * y + coef[2 * (n * C + c) + 1] * (squared ? 2.f * p[c] : 1.f));
       dot += g[c] * p[c];
     }
@@ -262,28 +261,8 @@ __global__ void ce_kernel(const float* z, const TT* y, int N, int C, long long V
       }
     }
   }
-  red[threadIdx.x] = local;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
+  block_sum_256(red, local);
   if (threadIdx.x == 0) part[blockIdx.x] = red[0];
-}
-__global__ void ce_finalize_kernel(const float* part, int B, double inv_count, float weight, float* loss, int accumulate) {
-  __shared__ double red[256];
-  double s = 0.0;
-  for (int b = threadIdx.x; b < B; b += blockDim.x) s += (double)part[b];
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int k = 128; k > 0; k >>= 1) {
-    if ((int)threadIdx.x < k) red[threadIdx.x] += red[threadIdx.x + k];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    const float v = (float)(red[0] * inv_count) * weight;
-    loss[0] = accumulate ? loss[0] + v : v;
-  }
 }
 
 extern "C" size_t mi355_ce_workspace(int64_t voxels) { (void)voxels; return CE_BLOCKS * sizeof(float); }
@@ -305,7 +284,7 @@ extern "C" int mi355_ce_fwd_bwd(const float* logits, const void* target, int32_t
     LAUNCH((ce_kernel<float>), dim3((unsigned)g), dim3(256), 0, stream, logits, (const float*)target, n, c, (long long)voxels, mode, gs, dlogits,
            accumulate_grad, (float*)ws);
   int rc = LAUNCH_CHECK(); if (rc) return rc;
-  LAUNCH(ce_finalize_kernel, dim3(1), dim3(256), 0, stream, (const float*)ws, (int)g, 1.0 / count, weight, loss, accumulate_loss);
+  LAUNCH(loss_finalize_kernel, dim3(1), dim3(256), 0, stream, (const float*)ws, (int)g, 1.0 / count, weight, loss, accumulate_loss);
   return LAUNCH_CHECK();
 }
 
@@ -341,47 +320,6 @@ extern "C" int mi355_dice_fwd_bwd(const float* logits, const void* target, int32
   return rc;
 }
 
-static int dice_ex_check(const mi355_dice_opts* o, int32_t n, int32_t c, int64_t voxels) {
-  if (!o || n <= 0 || c <= 0 || voxels <= 0) return MI355_EINVAL;
-  if (o->activation < MI355_DICE_ACT_NONE || o->activation > MI355_DICE_ACT_SOFTMAX) return MI355_EINVAL;
-  if (o->target_kind < MI355_DICE_TARGET_F32 || o->target_kind > MI355_DICE_TARGET_LABELS) return MI355_EINVAL;
-  if (o->reduction < MI355_DICE_REDUCE_MEAN || o->reduction > MI355_DICE_REDUCE_NONE) return MI355_EINVAL;
-  if (!o->include_background && c < 2) return MI355_EINVAL;
-  if (c > DICE_MAX_C || (size_t)n * c > 1024) return MI355_EUNSUPPORTED;
-  return MI355_OK;
-}
-
-extern "C" int mi355_dice_ex_forward(const mi355_dice_opts* o, const float* logits, const void* target, int32_t n, int32_t c, int64_t voxels,
-                                     float* loss, void* ws, size_t ws_bytes, void* stream) {
-  int rc = dice_ex_check(o, n, c, voxels); if (rc) return rc;
-  if (!logits || !target || !loss || !ws) return MI355_EINVAL;
-  if (ws_bytes < mi355_dice_workspace(n, c, voxels)) return MI355_EWORKSPACE;
-  const int NC = n * c, B = dice_blocks(voxels);
-  float* part = (float*)ws; float* stats = part + (size_t)NC * B * 3; float* coef = stats + (size_t)NC * 3;
-  LAUNCH(dice_ex_partial_kernel, dim3(B, n), dim3(256), 0, stream, logits, target, o->target_kind, (long long)voxels, c, o->activation,
-         o->squared_pred, part);
-  rc = LAUNCH_CHECK(); if (rc) return rc;
-  LAUNCH(dice_finalize_kernel, dim3(1), dim3(256), 0, stream, (const float*)part, B, n, c, o->batch, o->smooth_nr, o->smooth_dr, 1.0f,
-         MI355_DICE_PLAIN, o->include_background ? 0 : 1, stats, coef, loss, o->jaccard, o->class_weight, o->reduction);
-  return LAUNCH_CHECK();
-}
-
-extern "C" int mi355_dice_ex_backward(const mi355_dice_opts* o, const float* logits, const void* target, int32_t n, int32_t c, int64_t voxels,
-                                      const float* upstream, int32_t n_upstream, float* dlogits, const void* ws, void* stream) {
-  int rc = dice_ex_check(o, n, c, voxels); if (rc) return rc;
-  if (!logits || !target || !dlogits || !ws) return MI355_EINVAL;
-  const int ce = c - (o->include_background ? 0 : 1);
-  const int terms = o->reduction == MI355_DICE_REDUCE_NONE ? (o->batch ? ce : n * ce) : 1;
-  if (upstream && n_upstream != terms) return MI355_EINVAL;
-  const int NC = n * c, B = dice_blocks(voxels);
-  const float* coef = (const float*)ws + (size_t)NC * B * 3 + (size_t)NC * 3;
-  const long long total = (long long)n * voxels;
-  long long grid = (total + 255) / 256; if (grid > 16384) grid = 16384;
-  LAUNCH(dice_ex_grad_kernel, dim3((unsigned)grid), dim3(256), 0, stream, logits, target, o->target_kind, (long long)voxels, n, c, o->activation,
-         o->squared_pred, coef, upstream, n_upstream, o->batch, o->include_background ? 0 : 1, dlogits);
-  return LAUNCH_CHECK();
-}
-
 // ---- Tversky (monai.losses.TverskyLoss) on the extended Dice passes: the same three sums, another finaliser ----
 // tp = I, fp = P - I, fn = Y - I:  f = 1 - (I + snr) / D,  D = (1 - alpha - beta) I + alpha P + beta Y + sdr
 // df/dp = -[y D - (I + snr)((1 - alpha - beta) y + alpha)] / D^2 = -a y + b: the (a, b) pair dice_ex_grad_kernel consumes (squared off).
@@ -391,13 +329,7 @@ __global__ void tversky_finalize_kernel(const float* ws, int B, int N, int C, in
   __shared__ double sums[3 * 1024];
   __shared__ double fsum[256];
   const int NC = N * C;
-  for (int i = threadIdx.x; i < NC; i += blockDim.x) {
-    double a = 0.0, b = 0.0, c = 0.0;
-    for (int k = 0; k < B; ++k) { const float* p = ws + ((size_t)i * B + k) * 3; a += (double)p[0]; b += (double)p[1]; c += (double)p[2]; }
-    sums[3 * i] = a; sums[3 * i + 1] = b; sums[3 * i + 2] = c;
-    stats[3 * i] = (float)a; stats[3 * i + 1] = (float)b; stats[3 * i + 2] = (float)c;
-  }
-  __syncthreads();
+  dice_load_sums(ws, B, NC, sums, stats);
   double f = 0.0;
   const int Ce = C - c0;
   const int K = reduction != 0 ? 1 : (batch ? Ce : N * Ce);
@@ -419,51 +351,90 @@ __global__ void tversky_finalize_kernel(const float* ws, int B, int N, int C, in
       else f += term / K;
     }
   }
-  fsum[threadIdx.x] = f;
-  __syncthreads();
-  for (int s = blockDim.x / 2; s > 0; s >>= 1) { if ((int)threadIdx.x < s) fsum[threadIdx.x] += fsum[threadIdx.x + s]; __syncthreads(); }
-  if (threadIdx.x == 0 && reduction != 2) loss[0] = (float)fsum[0];
+  dice_store_loss(fsum, f, reduction != 2, loss);
 }
 
-static int tversky_check(const mi355_tversky_opts* o, int32_t n, int32_t c, int64_t voxels) {
-  if (!o || n <= 0 || c <= 0 || voxels <= 0) return MI355_EINVAL;
-  if (o->activation < MI355_DICE_ACT_NONE || o->activation > MI355_DICE_ACT_SOFTMAX) return MI355_EINVAL;
-  if (o->target_kind < MI355_DICE_TARGET_F32 || o->target_kind > MI355_DICE_TARGET_LABELS) return MI355_EINVAL;
-  if (o->reduction < MI355_DICE_REDUCE_MEAN || o->reduction > MI355_DICE_REDUCE_NONE) return MI355_EINVAL;
-  if (!(o->alpha == o->alpha) || !(o->beta == o->beta)) return MI355_EINVAL;                        // NaN
-  if (!o->include_background && c < 2) return MI355_EINVAL;
+// ---- the two-call entry points: mi355_dice_ex_* and mi355_tversky_* differ in the finaliser (and Tversky sums without squaring) ----
+// the option fields mi355_dice_opts and mi355_tversky_opts have in common (Tversky: squared_pred = 0)
+struct TwoCallOpts { int activation, target_kind, batch, squared_pred, include_background, reduction; };
+static TwoCallOpts two_call_opts(const mi355_dice_opts* o) {
+  return {o->activation, o->target_kind, o->batch, o->squared_pred, o->include_background, o->reduction};
+}
+static TwoCallOpts two_call_opts(const mi355_tversky_opts* o) { return {o->activation, o->target_kind, o->batch, 0, o->include_background, o->reduction}; }
+
+static int two_call_check(const TwoCallOpts& o, int32_t n, int32_t c, int64_t voxels) {
+  if (n <= 0 || c <= 0 || voxels <= 0) return MI355_EINVAL;
+  if (o.activation < MI355_DICE_ACT_NONE || o.activation > MI355_DICE_ACT_SOFTMAX) return MI355_EINVAL;
+  if (o.target_kind < MI355_DICE_TARGET_F32 || o.target_kind > MI355_DICE_TARGET_LABELS) return MI355_EINVAL;
+  if (o.reduction < MI355_DICE_REDUCE_MEAN || o.reduction > MI355_DICE_REDUCE_NONE) return MI355_EINVAL;
+  if (!o.include_background && c < 2) return MI355_EINVAL;
   if (c > DICE_MAX_C || (size_t)n * c > 1024) return MI355_EUNSUPPORTED;
   return MI355_OK;
 }
+static bool tversky_numbers(const mi355_tversky_opts* o) { return o && o->alpha == o->alpha && o->beta == o->beta; }   // neither is NaN
 
-extern "C" int mi355_tversky_forward(const mi355_tversky_opts* o, const float* logits, const void* target, int32_t n, int32_t c, int64_t voxels,
-                                     float* loss, void* ws, size_t ws_bytes, void* stream) {
-  int rc = tversky_check(o, n, c, voxels); if (rc) return rc;
+// forward: the sums, then finalize(part, B, stats, coef) launches the finaliser of the loss
+template <class Finalize>
+static int two_call_forward(const TwoCallOpts& o, const float* logits, const void* target, int32_t n, int32_t c, int64_t voxels, float* loss,
+                            void* ws, size_t ws_bytes, void* stream, Finalize finalize) {
+  int rc = two_call_check(o, n, c, voxels); if (rc) return rc;
   if (!logits || !target || !loss || !ws) return MI355_EINVAL;
   if (ws_bytes < mi355_dice_workspace(n, c, voxels)) return MI355_EWORKSPACE;
   const int NC = n * c, B = dice_blocks(voxels);
   float* part = (float*)ws; float* stats = part + (size_t)NC * B * 3; float* coef = stats + (size_t)NC * 3;
-  LAUNCH(dice_ex_partial_kernel, dim3(B, n), dim3(256), 0, stream, logits, target, o->target_kind, (long long)voxels, c, o->activation, 0, part);
+  LAUNCH(dice_ex_partial_kernel, dim3(B, n), dim3(256), 0, stream, logits, target, o.target_kind, (long long)voxels, c, o.activation,
+         o.squared_pred, part);
   rc = LAUNCH_CHECK(); if (rc) return rc;
-  LAUNCH(tversky_finalize_kernel, dim3(1), dim3(256), 0, stream, (const float*)part, B, n, c, o->batch, o->alpha, o->beta, o->smooth_nr,
-         o->smooth_dr, o->include_background ? 0 : 1, stats, coef, loss, o->reduction);
+  finalize((const float*)part, B, stats, coef);
   return LAUNCH_CHECK();
 }
 
-extern "C" int mi355_tversky_backward(const mi355_tversky_opts* o, const float* logits, const void* target, int32_t n, int32_t c, int64_t voxels,
-                                      const float* upstream, int32_t n_upstream, float* dlogits, const void* ws, void* stream) {
-  int rc = tversky_check(o, n, c, voxels); if (rc) return rc;
+static int two_call_backward(const TwoCallOpts& o, const float* logits, const void* target, int32_t n, int32_t c, int64_t voxels,
+                             const float* upstream, int32_t n_upstream, float* dlogits, const void* ws, void* stream) {
+  int rc = two_call_check(o, n, c, voxels); if (rc) return rc;
   if (!logits || !target || !dlogits || !ws) return MI355_EINVAL;
-  const int ce = c - (o->include_background ? 0 : 1);
-  const int terms = o->reduction == MI355_DICE_REDUCE_NONE ? (o->batch ? ce : n * ce) : 1;
+  const int ce = c - (o.include_background ? 0 : 1);
+  const int terms = o.reduction == MI355_DICE_REDUCE_NONE ? (o.batch ? ce : n * ce) : 1;
   if (upstream && n_upstream != terms) return MI355_EINVAL;
   const int NC = n * c, B = dice_blocks(voxels);
   const float* coef = (const float*)ws + (size_t)NC * B * 3 + (size_t)NC * 3;
   const long long total = (long long)n * voxels;
   long long grid = (total + 255) / 256; if (grid > 16384) grid = 16384;
-  LAUNCH(dice_ex_grad_kernel, dim3((unsigned)grid), dim3(256), 0, stream, logits, target, o->target_kind, (long long)voxels, n, c, o->activation,
-         0, coef, upstream, n_upstream, o->batch, o->include_background ? 0 : 1, dlogits);
+  LAUNCH(dice_ex_grad_kernel, dim3((unsigned)grid), dim3(256), 0, stream, logits, target, o.target_kind, (long long)voxels, n, c, o.activation,
+         o.squared_pred, coef, upstream, n_upstream, o.batch, o.include_background ? 0 : 1, dlogits);
   return LAUNCH_CHECK();
+}
+
+extern "C" int mi355_dice_ex_forward(const mi355_dice_opts* o, const float* logits, const void* target, int32_t n, int32_t c, int64_t voxels,
+                                     float* loss, void* ws, size_t ws_bytes, void* stream) {
+  if (!o) return MI355_EINVAL;
+  return two_call_forward(two_call_opts(o), logits, target, n, c, voxels, loss, ws, ws_bytes, stream,
+                          [=](const float* part, int B, float* stats, float* coef) {
+    LAUNCH(dice_finalize_kernel, dim3(1), dim3(256), 0, stream, part, B, n, c, o->batch, o->smooth_nr, o->smooth_dr, 1.0f,
+           MI355_DICE_PLAIN, o->include_background ? 0 : 1, stats, coef, loss, o->jaccard, o->class_weight, o->reduction);
+  });
+}
+
+extern "C" int mi355_dice_ex_backward(const mi355_dice_opts* o, const float* logits, const void* target, int32_t n, int32_t c, int64_t voxels,
+                                      const float* upstream, int32_t n_upstream, float* dlogits, const void* ws, void* stream) {
+  if (!o) return MI355_EINVAL;
+  return two_call_backward(two_call_opts(o), logits, target, n, c, voxels, upstream, n_upstream, dlogits, ws, stream);
+}
+
+extern "C" int mi355_tversky_forward(const mi355_tversky_opts* o, const float* logits, const void* target, int32_t n, int32_t c, int64_t voxels,
+                                     float* loss, void* ws, size_t ws_bytes, void* stream) {
+  if (!tversky_numbers(o)) return MI355_EINVAL;
+  return two_call_forward(two_call_opts(o), logits, target, n, c, voxels, loss, ws, ws_bytes, stream,
+                          [=](const float* part, int B, float* stats, float* coef) {
+    LAUNCH(tversky_finalize_kernel, dim3(1), dim3(256), 0, stream, part, B, n, c, o->batch, o->alpha, o->beta, o->smooth_nr,
+           o->smooth_dr, o->include_background ? 0 : 1, stats, coef, loss, o->reduction);
+  });
+}
+
+extern "C" int mi355_tversky_backward(const mi355_tversky_opts* o, const float* logits, const void* target, int32_t n, int32_t c, int64_t voxels,
+                                      const float* upstream, int32_t n_upstream, float* dlogits, const void* ws, void* stream) {
+  if (!tversky_numbers(o)) return MI355_EINVAL;
+  return two_call_backward(two_call_opts(o), logits, target, n, c, voxels, upstream, n_upstream, dlogits, ws, stream);
 }
 
 __global__ void adam_kernel(float* p, const float* g, float* m, float* v, long long count, float step_size, float b1, float omb1, float b2,

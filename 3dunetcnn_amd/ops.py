@@ -876,16 +876,28 @@ class Backend:
         return out, lout
 
     # -- loss / optimizer ----------------------------------------------------------------------------------------
+    @staticmethod
+    def _target_kind(target):
+        """MI355_DICE_TARGET_*: 0 fp32, 1 uint8 (both of the logits' shape), 2 an int32 label map"""
+        return 2 if target.dtype == torch.int32 else (1 if target.dtype == torch.uint8 else 0)
+
+    @staticmethod
+    def _loss_dims(logits, target, labels=False):
+        """the assertion every loss pass starts with -> (n, c, voxels). target: uint8 / fp32 of the logits' shape, or (`labels`) an int32
+        label map [n, 1, ...] / [n, ...]"""
+        assert logits.is_contiguous() and target.is_contiguous() and logits.dtype == torch.float32
+        n, c, vox = logits.shape[0], logits.shape[1], logits[0, 0].numel()
+        assert (labels and target.dtype == torch.int32 and target.numel() == n * vox) or \
+            (target.dtype in (torch.uint8, torch.float32) and target.shape == logits.shape)
+        return n, c, vox
+
     def dice(self, logits, target, sigmoid=True, batch=False, squared_pred=False, smooth_nr=1e-5, smooth_dr=1e-5,
              want_grad=True, grad_scale=1.0, generalized=False, include_background=True):
-        assert logits.is_contiguous() and target.is_contiguous() and logits.dtype == torch.float32
-        assert target.dtype in (torch.uint8, torch.float32) and target.shape == logits.shape
-        n, c = logits.shape[0], logits.shape[1]
-        vox = logits[0, 0].numel()
+        n, c, vox = self._loss_dims(logits, target)
         loss = torch.empty(1, dtype=torch.float32, device=self.device)
         dlogits = torch.empty_like(logits) if want_grad else None
         ws = self.ws(self.lib.mi355_dice_workspace(n, c, vox))
-        check(self.lib.mi355_dice_fwd_bwd(logits.data_ptr(), target.data_ptr(), 1 if target.dtype == torch.uint8 else 0, n, c, vox,
+        check(self.lib.mi355_dice_fwd_bwd(logits.data_ptr(), target.data_ptr(), self._target_kind(target), n, c, vox,
                                           int(sigmoid), int(batch), int(squared_pred), int(generalized), int(include_background), smooth_nr,
                                           smooth_dr, loss.data_ptr(),
                                           _p(dlogits), grad_scale, ws.data_ptr(), ws.numel() * 4, self.stream()), "dice_fwd_bwd")
@@ -894,54 +906,70 @@ class Backend:
     DICE_ACT = {None: 0, "sigmoid": 1, "softmax": 2}
     DICE_REDUCE = {"mean": 0, "sum": 1, "none": 2}
 
-    def _dice_opts(self, target, activation, batch, squared_pred, include_background, jaccard, reduction, smooth_nr, smooth_dr, class_weight):
-        kind = 2 if target.dtype == torch.int32 else (1 if target.dtype == torch.uint8 else 0)
-        return MiDiceOpts(self.DICE_ACT[activation], kind, int(batch), int(squared_pred), int(include_background), int(jaccard),
-                          self.DICE_REDUCE[reduction], float(smooth_nr), float(smooth_dr), _p(class_weight))
+    def _two_call_forward(self, entry, o, keep, logits, target, batch, include_background, reduction):
+        """mi355_<entry>: the sums of the extended Dice passes + the finalisation of `entry` -> (loss values [1] or one per term, state for
+        _two_call_backward: the opts structure, the workspace -- kept, backward reads its coefficients -- and what `o` points into)"""
+        n, c, vox = self._loss_dims(logits, target, labels=True)
+        ce = c - (0 if include_background else 1)
+        terms = (ce if batch else n * ce) if reduction == "none" else 1
+        loss = torch.empty(terms, dtype=torch.float32, device=self.device)
+        ws = torch.empty(self.lib.mi355_dice_workspace(n, c, vox) // 4, dtype=torch.float32, device=self.device)
+        check(getattr(self.lib, "mi355_" + entry)(ctypes.byref(o), logits.data_ptr(), target.data_ptr(), n, c, vox, loss.data_ptr(), ws.data_ptr(),
+                                                  ws.numel() * 4, self.stream()), entry)
+        return loss, (o, ws, keep)
+
+    def _two_call_backward(self, entry, logits, target, state, upstream):
+        """d(sum_t upstream[t] * loss[t]) / d(logits); upstream: fp32 tensor with one value per loss value."""
+        o, ws, _keep = state
+        n, c, vox = logits.shape[0], logits.shape[1], logits[0, 0].numel()
+        dlogits = torch.empty_like(logits)
+        upstream = upstream.reshape(-1).contiguous().float()
+        check(getattr(self.lib, "mi355_" + entry)(ctypes.byref(o), logits.data_ptr(), target.data_ptr(), n, c, vox, upstream.data_ptr(),
+                                                  upstream.numel(), dlogits.data_ptr(), ws.data_ptr(), self.stream()), entry)
+        return dlogits
 
     def dice_ex_forward(self, logits, target, activation="sigmoid", batch=False, squared_pred=False, include_background=True, jaccard=False,
                         reduction="mean", smooth_nr=1e-5, smooth_dr=1e-5, class_weight=None):
         """monai DiceLoss with the options the fused mi355_dice_fwd_bwd does not carry. target: same shape as the logits (uint8 / fp32) or
         an int32 label map [n, 1, ...] (to_onehot_y). Returns (loss values [1] or one per term, state for dice_ex_backward)."""
-        assert logits.is_contiguous() and target.is_contiguous() and logits.dtype == torch.float32
-        n, c = logits.shape[0], logits.shape[1]
-        vox = logits[0, 0].numel()
-        assert (target.dtype == torch.int32 and target.numel() == n * vox) or (target.dtype in (torch.uint8, torch.float32) and target.shape == logits.shape)
-        ce = c - (0 if include_background else 1)
-        terms = (ce if batch else n * ce) if reduction == "none" else 1
-        loss = torch.empty(terms, dtype=torch.float32, device=self.device)
-        o = self._dice_opts(target, activation, batch, squared_pred, include_background, jaccard, reduction, smooth_nr, smooth_dr, class_weight)
-        ws = torch.empty(self.lib.mi355_dice_workspace(n, c, vox) // 4, dtype=torch.float32, device=self.device)   # kept for backward
-        check(self.lib.mi355_dice_ex_forward(ctypes.byref(o), logits.data_ptr(), target.data_ptr(), n, c, vox, loss.data_ptr(), ws.data_ptr(),
-                                             ws.numel() * 4, self.stream()), "dice_ex_forward")
-        return loss, (o, ws, class_weight)
+        o = MiDiceOpts(self.DICE_ACT[activation], self._target_kind(target), int(batch), int(squared_pred), int(include_background), int(jaccard),
+                       self.DICE_REDUCE[reduction], float(smooth_nr), float(smooth_dr), _p(class_weight))
+        return self._two_call_forward("dice_ex_forward", o, class_weight, logits, target, batch, include_background, reduction)
 
     def dice_ex_backward(self, logits, target, state, upstream):
         """d(sum_t upstream[t] * loss[t]) / d(logits); upstream: fp32 tensor with one value per loss value."""
-        o, ws, _keep = state
-        n, c = logits.shape[0], logits.shape[1]
-        vox = logits[0, 0].numel()
-        dlogits = torch.empty_like(logits)
-        upstream = upstream.reshape(-1).contiguous().float()
-        check(self.lib.mi355_dice_ex_backward(ctypes.byref(o), logits.data_ptr(), target.data_ptr(), n, c, vox, upstream.data_ptr(),
-                                              upstream.numel(), dlogits.data_ptr(), ws.data_ptr(), self.stream()), "dice_ex_backward")
-        return dlogits
+        return self._two_call_backward("dice_ex_backward", logits, target, state, upstream)
 
-    def cross_entropy(self, logits, target, mode="softmax", weight=1.0, loss=None, dlogits=None, want_grad=True, grad_scale=1.0):
-        """mode "softmax": CrossEntropyLoss(mean) with probability targets; "bce": BCEWithLogitsLoss(mean). `loss` / `dlogits`
-        given: the weighted CE value / gradient is ADDED to them (fusing with a Dice term); else fresh tensors are returned."""
-        assert logits.is_contiguous() and target.is_contiguous() and logits.dtype == torch.float32
-        assert target.dtype in (torch.uint8, torch.float32) and target.shape == logits.shape
-        n, c = logits.shape[0], logits.shape[1]
-        vox = logits[0, 0].numel()
+    def tversky_forward(self, logits, target, activation="sigmoid", alpha=0.5, beta=0.5, batch=False, include_background=True,
+                        reduction="mean", smooth_nr=1e-5, smooth_dr=1e-5):
+        """monai TverskyLoss on the extended Dice passes. target as in dice_ex_forward. Returns (loss values [1] or one per term, state for
+        tversky_backward)."""
+        o = MiTverskyOpts(self.DICE_ACT[activation], self._target_kind(target), int(batch), int(include_background), self.DICE_REDUCE[reduction],
+                          float(alpha), float(beta), float(smooth_nr), float(smooth_dr))
+        return self._two_call_forward("tversky_forward", o, None, logits, target, batch, include_background, reduction)
+
+    def tversky_backward(self, logits, target, state, upstream):
+        """d(sum_t upstream[t] * loss[t]) / d(logits); upstream: fp32 tensor with one value per loss value."""
+        return self._two_call_backward("tversky_backward", logits, target, state, upstream)
+
+    def _onto(self, logits, loss, dlogits, want_grad):
+        """accumulate-or-allocate of a pass that lands on top of a Dice term: `loss` / `dlogits` given are added to, else fresh tensors
+        -> (loss, dlogits, accumulate_loss, accumulate_grad)"""
         acc_l, acc_g = loss is not None, dlogits is not None
         if loss is None:
             loss = torch.empty(1, dtype=torch.float32, device=self.device)
         if dlogits is None and want_grad:
             dlogits = torch.empty_like(logits)
+        return loss, dlogits, int(acc_l), int(acc_g)
+
+    def cross_entropy(self, logits, target, mode="softmax", weight=1.0, loss=None, dlogits=None, want_grad=True, grad_scale=1.0):
+        """mode "softmax": CrossEntropyLoss(mean) with probability targets; "bce": BCEWithLogitsLoss(mean). `loss` / `dlogits`
+        given: the weighted CE value / gradient is ADDED to them (fusing with a Dice term); else fresh tensors are returned."""
+        n, c, vox = self._loss_dims(logits, target)
+        loss, dlogits, acc_l, acc_g = self._onto(logits, loss, dlogits, want_grad)
         ws = self.ws(self.lib.mi355_ce_workspace(vox))
-        check(self.lib.mi355_ce_fwd_bwd(logits.data_ptr(), target.data_ptr(), 1 if target.dtype == torch.uint8 else 0, n, c, vox,
-                                        {"softmax": 0, "bce": 1}[mode], float(weight), loss.data_ptr(), int(acc_l), _p(dlogits), int(acc_g),
+        check(self.lib.mi355_ce_fwd_bwd(logits.data_ptr(), target.data_ptr(), self._target_kind(target), n, c, vox,
+                                        {"softmax": 0, "bce": 1}[mode], float(weight), loss.data_ptr(), acc_l, _p(dlogits), acc_g,
                                         float(grad_scale), ws.data_ptr(), ws.numel() * 4, self.stream()), "ce_fwd_bwd")
         return loss, dlogits
 
@@ -950,55 +978,17 @@ class Backend:
         """Focal loss (mi355_focal_fwd_bwd). mode "sigmoid" | "softmax"; target: the logits' shape (uint8 / fp32) or an int32 label map
         [n, 1, ...] / [n, ...]; reduction "mean" | "sum" (sum over (n, c) of the spatial mean); class_weight: device fp32, one factor per
         counted class. `loss` / `dlogits` given: weight x the value / gradient is ADDED to them (on top of a Dice term); else fresh tensors."""
-        assert logits.is_contiguous() and target.is_contiguous() and logits.dtype == torch.float32
-        n, c = logits.shape[0], logits.shape[1]
-        vox = logits[0, 0].numel()
-        assert (target.dtype == torch.int32 and target.numel() == n * vox) or (target.dtype in (torch.uint8, torch.float32) and target.shape == logits.shape)
+        n, c, vox = self._loss_dims(logits, target, labels=True)
         assert class_weight is None or (class_weight.dtype == torch.float32 and class_weight.is_contiguous()
                                         and class_weight.numel() == c - (0 if include_background else 1))
-        kind = 2 if target.dtype == torch.int32 else (1 if target.dtype == torch.uint8 else 0)
-        o = MiFocalOpts({"sigmoid": 0, "softmax": 1}[mode], kind, int(include_background), {"mean": 0, "sum": 1}[reduction],
+        o = MiFocalOpts({"sigmoid": 0, "softmax": 1}[mode], self._target_kind(target), int(include_background), {"mean": 0, "sum": 1}[reduction],
                         int(alpha is not None), float(gamma), float(alpha if alpha is not None else 0.0), _p(class_weight))
-        acc_l, acc_g = loss is not None, dlogits is not None
-        if loss is None:
-            loss = torch.empty(1, dtype=torch.float32, device=self.device)
-        if dlogits is None and want_grad:
-            dlogits = torch.empty_like(logits)
+        loss, dlogits, acc_l, acc_g = self._onto(logits, loss, dlogits, want_grad)
         ws = self.ws(_lib.FOCAL_SCRATCH_BYTES)
         check(self.lib.mi355_focal_fwd_bwd(ctypes.byref(o), logits.data_ptr(), target.data_ptr(), n, c, vox, float(weight), loss.data_ptr(),
-                                           int(acc_l), _p(dlogits), int(acc_g), float(grad_scale), ws.data_ptr(), ws.numel() * 4,
+                                           acc_l, _p(dlogits), acc_g, float(grad_scale), ws.data_ptr(), ws.numel() * 4,
                                            self.stream()), "focal_fwd_bwd")
         return loss, dlogits
-
-    def tversky_forward(self, logits, target, activation="sigmoid", alpha=0.5, beta=0.5, batch=False, include_background=True,
-                        reduction="mean", smooth_nr=1e-5, smooth_dr=1e-5):
-        """monai TverskyLoss on the extended Dice passes. target as in dice_ex_forward. Returns (loss values [1] or one per term, state for
-        tversky_backward)."""
-        assert logits.is_contiguous() and target.is_contiguous() and logits.dtype == torch.float32
-        n, c = logits.shape[0], logits.shape[1]
-        vox = logits[0, 0].numel()
-        assert (target.dtype == torch.int32 and target.numel() == n * vox) or (target.dtype in (torch.uint8, torch.float32) and target.shape == logits.shape)
-        ce = c - (0 if include_background else 1)
-        terms = (ce if batch else n * ce) if reduction == "none" else 1
-        loss = torch.empty(terms, dtype=torch.float32, device=self.device)
-        kind = 2 if target.dtype == torch.int32 else (1 if target.dtype == torch.uint8 else 0)
-        o = MiTverskyOpts(self.DICE_ACT[activation], kind, int(batch), int(include_background), self.DICE_REDUCE[reduction], float(alpha),
-                          float(beta), float(smooth_nr), float(smooth_dr))
-        ws = torch.empty(self.lib.mi355_dice_workspace(n, c, vox) // 4, dtype=torch.float32, device=self.device)   # kept for backward
-        check(self.lib.mi355_tversky_forward(ctypes.byref(o), logits.data_ptr(), target.data_ptr(), n, c, vox, loss.data_ptr(), ws.data_ptr(),
-                                             ws.numel() * 4, self.stream()), "tversky_forward")
-        return loss, (o, ws)
-
-    def tversky_backward(self, logits, target, state, upstream):
-        """d(sum_t upstream[t] * loss[t]) / d(logits); upstream: fp32 tensor with one value per loss value."""
-        o, ws = state
-        n, c = logits.shape[0], logits.shape[1]
-        vox = logits[0, 0].numel()
-        dlogits = torch.empty_like(logits)
-        upstream = upstream.reshape(-1).contiguous().float()
-        check(self.lib.mi355_tversky_backward(ctypes.byref(o), logits.data_ptr(), target.data_ptr(), n, c, vox, upstream.data_ptr(),
-                                              upstream.numel(), dlogits.data_ptr(), ws.data_ptr(), self.stream()), "tversky_backward")
-        return dlogits
 
     def adam_step(self, p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0):
         check(self.lib.mi355_adam_step(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), lr, beta1, beta2, eps,

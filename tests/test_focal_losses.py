@@ -284,10 +284,10 @@ def test_launch_counts(emu_backend):
     empty, full = torch.zeros(2, 3, 6, 5, 7, dtype=torch.uint8), torch.ones(2, 3, 6, 5, 7, dtype=torch.uint8)
     labels = torch.randint(0, 3, (2, 1, 6, 5, 7), generator=torch.Generator().manual_seed(2))
     seen = [run(losses.HipFocalLoss(), t) for t in (empty, full)]
-    assert seen[0] == seen[1] == ["(focal_kernel<0>)", "focal_finalize_kernel"], seen
-    assert run(losses.HipFocalLoss(use_softmax=True, to_onehot_y=True), labels) == ["(focal_kernel<1>)", "focal_finalize_kernel"]      # label maps are read as they are
-    is_ce = lambda k: k == "ce_finalize_kernel" or k.startswith("(ce_kernel<")
-    is_focal = lambda k: k == "focal_finalize_kernel" or k.startswith("(focal_kernel<")
+    assert seen[0] == seen[1] == ["(focal_kernel<0>)", "loss_finalize_kernel"], seen
+    assert run(losses.HipFocalLoss(use_softmax=True, to_onehot_y=True), labels) == ["(focal_kernel<1>)", "loss_finalize_kernel"]      # label maps are read as they are
+    is_ce = lambda k: k == "loss_finalize_kernel" or k.startswith("(ce_kernel<")
+    is_focal = lambda k: k == "loss_finalize_kernel" or k.startswith("(focal_kernel<")
     masked = lambda ks, hit: ["*" if hit(k) else k for k in ks]
     for kw, t in ((dict(sigmoid=True), empty), (dict(sigmoid=True), full), (dict(sigmoid=True, jaccard=True, reduction="sum"), full),
                   (dict(softmax=True, to_onehot_y=True), labels)):
@@ -295,6 +295,11 @@ def test_launch_counts(emu_backend):
         assert sum(map(is_ce, ce)) == 2 and sum(map(is_focal, fo)) == 2 and masked(fo, is_focal) == masked(ce, is_ce), (kw, ce, fo)
     tv = [run(losses.HipTverskyLoss(sigmoid=True), t) for t in (empty, full)]
     assert tv[0] == tv[1] == ["dice_ex_partial_kernel", "tversky_finalize_kernel", "dice_ex_grad_kernel"], tv
+    fused = ["dice_partial_kernel", "dice_finalize_kernel", "dice_grad_kernel"]
+    assert run(losses.HipDiceLoss(sigmoid=True), full) == fused                                    # the training step's loss: one call
+    assert run(losses.HipGeneralizedDiceLoss(sigmoid=True), full) == fused
+    assert run(losses.HipDiceLoss(softmax=True), full) == ["dice_ex_partial_kernel", "dice_finalize_kernel", "dice_ex_grad_kernel"]
+    assert run(losses.HipCrossEntropyLoss(), labels) == ["one_hot_kernel", "one_hot_kernel", "(ce_kernel<unsigned char>)", "loss_finalize_kernel"]
 
 
 # ---- registration --------------------------------------------------------------------------------------------------------------------------

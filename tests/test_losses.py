@@ -83,6 +83,25 @@ def test_losses_gpu(name, mk, ref, c):
     _check(mk(), ref, None, "cuda", 2, c, (40, 48, 36), name)
 
 
+def _check_17_channels(be, dev):
+    """the one-call fused path carries any channel count with n * c <= 1024; only the two-call form stops at 16 classes"""
+    _check(losses.HipDiceLoss(sigmoid=True), lambda z, t: O.dice_loss(z, t, True), be, dev, 1, 17, (5, 4, 6))
+    crit = losses.HipDiceLoss(softmax=True)
+    crit._be = be if be is not None else object()
+    z, t = _data(1, 17, (5, 4, 6))
+    with pytest.raises(NotImplementedError, match="more than 16 classes"):
+        crit(z.to(dev), t.to(dev))
+
+
+def test_fused_dice_17_channels_on_emulator(emu_backend):
+    _check_17_channels(emu_backend, "cpu")
+
+
+@pytest.mark.gpu
+def test_fused_dice_17_channels_gpu():
+    _check_17_channels(None, "cuda")
+
+
 # monai DiceLoss options beyond the shipped configuration (the reference passes the config's loss kwargs straight to the class:
 # unet3d/scripts/script_utils.py:61-77): (constructor kwargs, channels, label-map target?)
 EX_CASES = [
@@ -206,3 +225,88 @@ def test_cross_entropy_index_targets_out_of_range_are_flagged_on_request():
     with pytest.raises(ValueError, match="outside"):
         crit(z, t)
 
+
+
+def test_weight_timing(emu_backend):
+    """HipDiceLoss takes a negative weight at construction and raises at forward (MONAI's DiceLoss), and weights more than one counted
+    class only; the focal family raises at construction as well and always applies the weight."""
+    crit = losses.HipDiceLoss(sigmoid=True, weight=[1.0, -1.0, 1.0])
+    crit._be = object()
+    with pytest.raises(ValueError, match="no less than 0"):
+        crit(torch.zeros(1, 3, 4, 4, 4), torch.zeros(1, 3, 4, 4, 4))
+    for cls in (losses.HipFocalLoss, losses.HipDiceFocalLoss):
+        with pytest.raises(ValueError, match="no less than 0"):
+            cls(weight=[1.0, -1.0, 1.0])
+    z, t = _data(2, 2, (9, 8, 10))
+
+    def value(crit):
+        crit._be = emu_backend
+        return crit(z, t)
+    assert torch.equal(value(losses.HipDiceLoss(sigmoid=True, weight=[2.0], include_background=False)),
+                       value(losses.HipDiceLoss(sigmoid=True, include_background=False)))
+    a, b = float(value(losses.HipFocalLoss(weight=[2.0], include_background=False))), float(value(losses.HipFocalLoss(include_background=False)))
+    assert abs(a - 2.0 * b) < 1e-6 * abs(b) and b > 0.0, (a, b)
+
+
+def test_state_dict_keys_and_round_trip():
+    for cls in (losses.HipDiceLoss, losses.HipFocalLoss, losses.HipDiceFocalLoss):
+        crit = cls(weight=[0.5, 1.0, 2.0])
+        assert list(crit.state_dict()) == ["class_weight"]
+        other = cls(weight=[1.0, 1.0, 1.0])
+        other.load_state_dict(crit.state_dict())
+        assert torch.equal(other.class_weight, torch.tensor([0.5, 1.0, 2.0]))
+        assert list(cls().state_dict()) == []
+        cls().load_state_dict(cls().state_dict())
+    for crit in (losses.HipTverskyLoss(), losses.HipDiceCELoss(sigmoid=True), losses.HipBCEWithLogitsLoss(), losses.HipCrossEntropyLoss(),
+                 losses.HipGeneralizedDiceLoss(sigmoid=True)):
+        assert len(crit.state_dict()) == 0
+        crit.load_state_dict({})
+
+
+# two faults at once: which check speaks first. (module, constructor kwargs, logits shape or None = the constructor raises, target shape,
+# exception, message fragment)
+Z3, Z17, Z1 = (1, 3, 4, 4, 4), (1, 17, 2, 2, 2), (1, 1, 2, 2, 2)
+PRECEDENCE = [
+    ("focal_17ch_before_target_shape", "HipFocalLoss", {}, Z17, (1, 3, 2, 2, 2), NotImplementedError, "more than 16 classes"),
+    ("tversky_17ch_before_target_shape", "HipTverskyLoss", {}, Z17, (1, 3, 2, 2, 2), NotImplementedError, "more than 16 classes"),
+    ("dice_target_shape_before_17ch", "HipDiceLoss", dict(softmax=True), Z17, (1, 3, 2, 2, 2), AssertionError, "different shape"),
+    ("dicece_target_shape_before_17ch", "HipDiceCELoss", dict(sigmoid=True), Z17, (1, 3, 2, 2, 2), AssertionError, "different shape"),
+    ("dice_single_channel_before_weight", "HipDiceLoss", dict(include_background=False, weight=[1.0, 2.0]), Z1, Z1, ValueError,
+     "single channel prediction"),
+    ("dice_weight_length_before_target_shape", "HipDiceLoss", dict(sigmoid=True, weight=[1.0, 2.0]), Z3, (1, 2, 4, 4, 4), ValueError,
+     "length of the `weight` sequence"),
+    ("dice_weight_length_before_sign", "HipDiceLoss", dict(sigmoid=True, weight=[1.0, -2.0]), Z3, Z3, ValueError, "length of the `weight` sequence"),
+    ("dicefocal_target_shape_before_weight_length", "HipDiceFocalLoss", dict(sigmoid=True, weight=[1.0, 2.0]), Z3, (1, 2, 4, 4, 4),
+     AssertionError, "different shape"),
+    ("focal_target_shape_before_weight_length", "HipFocalLoss", dict(weight=[1.0, 2.0]), Z3, (1, 2, 4, 4, 4), AssertionError, "different shape"),
+    ("tversky_single_channel_before_target_shape", "HipTverskyLoss", dict(include_background=False), Z1, (1, 2, 2, 2, 2), ValueError,
+     "single channel prediction"),
+    ("dicece_other_act_and_reduction", "HipDiceCELoss", dict(reduction="median", other_act=torch.tanh), None, None, NotImplementedError,
+     "does not implement: other_act"),
+    ("dicece_reduction_and_weight", "HipDiceCELoss", dict(reduction="median", weight=[1.0, 2.0]), None, None, NotImplementedError,
+     "does not implement: reduction, weight"),
+    ("dicece_unsupported_before_lambdas", "HipDiceCELoss", dict(label_smoothing=0.1, lambda_dice=-1.0), None, None, NotImplementedError,
+     "does not implement: label_smoothing"),
+    ("dice_other_act_before_reduction", "HipDiceLoss", dict(reduction="median", other_act=torch.tanh), None, None, NotImplementedError, "other_act"),
+    ("dicefocal_other_act_before_reduction", "HipDiceFocalLoss", dict(reduction="median", other_act=torch.tanh), None, None,
+     NotImplementedError, "other_act"),
+    ("dicefocal_reduction_before_gamma", "HipDiceFocalLoss", dict(reduction="none", gamma=-1.0), None, None, NotImplementedError, "reduction"),
+    ("dicefocal_lambdas_before_weight_sign", "HipDiceFocalLoss", dict(lambda_dice=-1.0, weight=[1.0, -1.0]), None, None, ValueError,
+     "lambda_dice and lambda_focal"),
+    ("tversky_reduction_before_nan", "HipTverskyLoss", dict(reduction="median", alpha=float("nan")), None, None, ValueError, "Unsupported reduction"),
+    ("gdl_w_type_before_other_act", "HipGeneralizedDiceLoss", dict(w_type="simple", other_act=3), None, None, NotImplementedError, "w_type"),
+    ("gdl_reduction_name_before_options", "HipGeneralizedDiceLoss", dict(reduction="median", softmax=True), None, None, ValueError,
+     "Unsupported reduction"),
+]
+
+
+@pytest.mark.parametrize("name,cls,kw,zs,ts,exc,frag", PRECEDENCE, ids=[r[0] for r in PRECEDENCE])
+def test_precedence_of_checks(name, cls, kw, zs, ts, exc, frag):
+    if zs is None:
+        with pytest.raises(exc, match=frag):
+            getattr(losses, cls)(**kw)
+        return
+    crit = getattr(losses, cls)(**kw)
+    crit._be = object()                                        # every check here runs before any kernel
+    with pytest.raises(exc, match=frag):
+        crit(torch.zeros(zs), torch.zeros(ts))
