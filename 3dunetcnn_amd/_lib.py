@@ -166,9 +166,20 @@ SIGNATURES = {
                                  c_void_p]),
     "mi355_surface_stats": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_double, c_void_p, c_void_p, c_void_p,
                                            c_void_p]),
+    "mi355_percentiles": (ctypes.c_int, [c_void_p, c_int32, c_int64, POINTER(c_double), c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_void_p]),
+    "mi355_window": (ctypes.c_int, [c_void_p, c_int32, c_void_p, c_int32, c_int64, c_void_p, c_void_p, c_int32, c_float, c_float, c_void_p]),
+    "mi355_zscore_select": (ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int64, c_int32, c_float, c_int32, c_int32, c_int32, c_void_p,
+                                           c_void_p, c_void_p]),
+    "mi355_threshold_any": (ctypes.c_int, [c_void_p, c_int32, c_int64, c_void_p, c_void_p, c_void_p]),
 }
 SURFACE_SCRATCH_BYTES = 32832      # MI355_SURFACE_SCRATCH_BYTES of the header: scratch of mi355_surface_stats, per channel
 FOCAL_SCRATCH_BYTES = 4096         # MI355_FOCAL_SCRATCH_BYTES of the header: the block partials of mi355_focal_fwd_bwd
+PERCENTILE_MAX_Q = 4               # MI355_PERCENTILE_MAX_Q: percentiles per call of mi355_percentiles
+PERCENTILE_SCRATCH_BYTES = 32896   # MI355_PERCENTILE_SCRATCH_BYTES: scratch of mi355_percentiles, per channel
+ZSCORE_SELECT_SCRATCH_BYTES = 20512  # MI355_ZSCORE_SELECT_SCRATCH_BYTES: scratch of mi355_zscore_select, per channel
+WINDOW_CLAMP, WINDOW_RESCALE, WINDOW_SHIFT_FLOOR = 0, 1, 2      # MI355_WINDOW_*
+SELECT_ALL, SELECT_NONZERO, SELECT_ABS_ABOVE = 0, 1, 2          # MI355_SELECT_*
 
 
 def bind(cdll):

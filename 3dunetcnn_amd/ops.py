@@ -848,6 +848,64 @@ class Backend:
                                            self.stream()), "surface_stats")
         return out, n
 
+    # -- intensity normalisation: percentiles, windows, z-score over a selected set, any-channel threshold (csrc/intensity.hip) -----------
+    @staticmethod
+    def _volume_ok(x):
+        return x.is_contiguous() and x.dtype == torch.float32 and x.dim() >= 2
+
+    @staticmethod
+    def _per_channel_ok(t, c, like):
+        return t.is_contiguous() and t.dtype == torch.float32 and t.numel() == c and t.device == like.device
+
+    def percentiles(self, x, q, above=None, want_ranks=False):
+        """x fp32 [C, ...]; q: 1 .. 4 percentiles in [0, 100] (host floats); above: None or device fp32 [C] (only values strictly greater
+        take part). Returns (fp32 [C, len(q)], int32 [C] participating values, fp32 [C, len(q), 2] order statistics or None): numpy's
+        linear rule in double over an exact radix select. See mi355_percentiles."""
+        q = [float(v) for v in q]
+        assert self._volume_ok(x) and 1 <= len(q) <= _lib.PERCENTILE_MAX_Q
+        c, nq = x.shape[0], len(q)
+        assert above is None or self._per_channel_ok(above, c, x)
+        out = torch.empty(c, nq, dtype=torch.float32, device=x.device)
+        n = torch.empty(c, dtype=torch.int32, device=x.device)
+        ranks = torch.empty(c, nq, 2, dtype=torch.float32, device=x.device) if want_ranks else None
+        scratch = torch.empty(c * _lib.PERCENTILE_SCRATCH_BYTES // 8, dtype=torch.float64, device=x.device)
+        check(self.lib.mi355_percentiles(x.data_ptr(), c, x[0].numel(), (ctypes.c_double * nq)(*q), nq, _p(above), out.data_ptr(), _p(ranks),
+                                         n.data_ptr(), scratch.data_ptr(), self.stream()), "percentiles")
+        return out, n, ranks
+
+    def window(self, x, lo, hi, mode, floor=0.0, ceiling=1.0, channels=None):
+        """x fp32 [C, ...] (or [1, ...] with channels = the number of windows: every output channel reads the one input channel); lo, hi
+        device fp32 [channels]; mode _lib.WINDOW_CLAMP | WINDOW_RESCALE | WINDOW_SHIFT_FLOOR (hi may be None). Returns fp32
+        [channels, ...]. See mi355_window."""
+        assert self._volume_ok(x)
+        c = x.shape[0] if channels is None else int(channels)
+        assert x.shape[0] in (c, 1) and self._per_channel_ok(lo, c, x) and (hi is None or self._per_channel_ok(hi, c, x))
+        y = torch.empty((c,) + tuple(x.shape[1:]), dtype=torch.float32, device=x.device)
+        check(self.lib.mi355_window(x.data_ptr(), x.shape[0], y.data_ptr(), c, x[0].numel(), lo.data_ptr(), _p(hi), int(mode), float(floor),
+                                    float(ceiling), self.stream()), "window")
+        return y
+
+    def zscore_select(self, x, select, threshold=0.0, center=True, ddof=0, zero_std_to_one=False):
+        """x fp32 [C, ...] -> (y, int32 [C] selected voxels): per channel y = selected ? (x - (center ? mean : 0)) / std : x with the
+        moments over the selected voxels (_lib.SELECT_ALL | SELECT_NONZERO | SELECT_ABS_ABOVE with `threshold`). See mi355_zscore_select."""
+        assert self._volume_ok(x)
+        c = x.shape[0]
+        y = torch.empty_like(x)
+        n = torch.empty(c, dtype=torch.int32, device=x.device)
+        scratch = torch.empty(c * _lib.ZSCORE_SELECT_SCRATCH_BYTES // 8, dtype=torch.float64, device=x.device)
+        check(self.lib.mi355_zscore_select(x.data_ptr(), y.data_ptr(), c, x[0].numel(), int(select), float(threshold), int(bool(center)),
+                                           int(ddof), int(bool(zero_std_to_one)), n.data_ptr(), scratch.data_ptr(), self.stream()),
+              "zscore_select")
+        return y, n
+
+    def threshold_any(self, x, thr):
+        """x fp32 [C, ...], thr device fp32 [C] -> uint8 [...]: 1 where any channel exceeds its threshold."""
+        assert self._volume_ok(x) and self._per_channel_ok(thr, x.shape[0], x)
+        out = torch.empty(tuple(x.shape[1:]), dtype=torch.uint8, device=x.device)
+        check(self.lib.mi355_threshold_any(x.data_ptr(), x.shape[0], x[0].numel(), thr.data_ptr(), out.data_ptr(), self.stream()),
+              "threshold_any")
+        return out
+
     def augment_batch(self, image, label, matrices, gain=None, offset=None, out_shape=None, padding="border", normalize=False):
         """Training augmentation of a batch in two launches (mi355_augment_batch). image [N, Ci, D, H, W] fp32; label None or
         [N, Cl, D, H, W] uint8 / fp32; matrices [N, 3, 4] (or [N, 12]) fp32 ON THE DEVICE: output voxel -> source voxel, (z, y, x)

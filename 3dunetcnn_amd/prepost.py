@@ -3,7 +3,7 @@
   compile_one_hot_encoding      unet3d/utils/one_hot.py:7-37   (LabelMapToOneHot, transforms/one_hot.py:7-16)
   convert_one_hot_to_label_map  unet3d/utils/one_hot.py:44-118 (threshold / argmax / hierarchy decode)
   activate_and_decode           unet3d/predict/volumetric.py:151-156 + the decode above, one pass over the logits
-  normalize_intensity           MONAI NormalizeIntensityD(channel_wise=True, nonzero=False), datasets/segmentation.py:77-86
+  normalize_intensity           MONAI NormalizeIntensityD(channel_wise=True, nonzero=False | True), datasets/segmentation.py:77-86
 
   resize                        MONAI ResizeD(spatial_size, mode=("trilinear", "nearest")) = F.interpolate(size=...,
                                 align_corners=False), datasets/segmentation.py:63-68
@@ -18,6 +18,7 @@ Inputs and outputs live on the GPU; there is no CPU fallback.
 """
 import torch
 
+from . import _lib
 from . import ops as _ops
 
 
@@ -74,13 +75,19 @@ def activate_and_decode(logits, activation, labels, threshold=0.5, label_hierarc
 
 
 def normalize_intensity(image, channel_wise=True, nonzero=False, _backend=None):
-    """image [C, D, H, W] (one sample) or [N, C, D, H, W]."""
-    if nonzero or not channel_wise:
-        raise NotImplementedError("only channel_wise=True, nonzero=False (the shipped configs: brats2020_config.json:140-144)")
+    """image [C, D, H, W] (one sample) or [N, C, D, H, W]. nonzero=True (the usual setting for skull-stripped MR): the mean and the
+    standard deviation (ddof 0) are those of the nonzero voxels of a channel and only those voxels change; a standard deviation of 0
+    counts as 1 (MONAI's rule)."""
+    if not channel_wise:
+        raise NotImplementedError("only channel_wise=True (the shipped configs: brats2020_config.json:140-144)")
     be = _be(image, _backend)
+    if nonzero:
+        one = lambda x: be.zscore_select(x.float().contiguous(), _lib.SELECT_NONZERO, center=True, ddof=0, zero_std_to_one=True)[0]  # noqa: E731
+    else:
+        one = lambda x: be.zscore(x.float().contiguous())                                                                          # noqa: E731
     if image.dim() == 5:
-        return torch.stack([be.zscore(image[n].float().contiguous()) for n in range(image.shape[0])])
-    return be.zscore(image.float().contiguous())
+        return torch.stack([one(image[n]) for n in range(image.shape[0])])
+    return one(image)
 
 
 def resize(img, spatial_size, mode="trilinear", _backend=None):

@@ -574,6 +574,50 @@ int mi355_edt(const uint8_t* sites, int32_t invert, int32_t c, int32_t d, int32_
 int mi355_surface_stats(const uint8_t* edges_a, const uint8_t* edges_b, const float* dist2_ab, const float* dist2_ba, int32_t c,
                         int64_t voxels, double percentile, float* out, int32_t* n, void* scratch, void* stream);
 
+/* ---- percentile statistics, intensity windows, z-score over a selected set, any-channel threshold (csrc/intensity.hip) ---------------
+ * Intensity normalisation of one sample without leaving the device. Volumes are fp32 [c][voxels], every channel on its own,
+ * 1 <= c <= 65535, 1 <= voxels <= 2^31 - 2. Every buffer is the caller's and has a closed-form size; all functions enqueue on `stream`
+ * and return; a fixed number of launches whatever the data; integer atomics only and floating sums in index order, so two calls on the
+ * same input give the same bits. Null pointers (other than the optional ones), a scratch that is not 8-byte aligned, sizes out of range
+ * and unknown codes: MI355_EINVAL.
+ *
+ * mi355_percentiles: out[ch][j] = the q[j]-th percentile of the participating values of channel ch by numpy's default linear rule,
+ *   evaluated in double: position p = q / 100 * (n - 1), the order statistics lo, hi of rank floor(p) and floor(p) + 1 (clamped to
+ *   n - 1) by an exact radix select over the order-preserving key of the bit pattern, value = lo + (p - floor(p)) * (hi - lo) rounded
+ *   once to fp32; lo == hi (infinite ones included) gives lo. q: HOST double[nq], 1 <= nq <= MI355_PERCENTILE_MAX_Q, every 0 <= q <= 100
+ *   (NaN refused). above: NULL (every value takes part) or DEVICE float[c]: only values strictly greater than above[ch] take part (a NaN
+ *   value never does; a NaN threshold selects nothing). n int32 [c] = participating values. n == 0: NaN. A participating NaN makes every
+ *   percentile of its channel NaN (numpy's rule). -0 and +0 are equal values: either may come back. ranks: NULL or fp32 [c][nq][2] =
+ *   (lo, hi), NaN where the percentile is. scratch: c * MI355_PERCENTILE_SCRATCH_BYTES bytes, zeroed by the op. Ten launches.
+ * mi355_window: y[ch][v] from x[x_channels == 1 ? 0 : ch][v] and the DEVICE thresholds lo[c], hi[c]; x_channels is c or 1. Modes:
+ *   MI355_WINDOW_CLAMP        torch.clamp(x, lo, hi): a NaN voxel or bound gives NaN, lo > hi gives hi.
+ *   MI355_WINDOW_RESCALE      t = (x - lo) / (hi - lo) in fp32 (IEEE division); t < floor -> floor; t > ceiling -> ceiling; a NaN t stays.
+ *   MI355_WINDOW_SHIFT_FLOOR  x <= lo ? floor : x - lo (hi is not read and may be NULL).
+ *   y may be x when x_channels == c. One launch.
+ * mi355_zscore_select: per channel, over the voxels chosen by `select` (MI355_SELECT_ALL; MI355_SELECT_NONZERO: x != 0;
+ *   MI355_SELECT_ABS_ABOVE: |x| > threshold, threshold not NaN), the count n, the mean and the standard deviation with ddof 0 or 1, in
+ *   double; y = selected ? (x - (center ? mean : 0)) / std : x, formed in double and rounded once; voxels not selected are copied bit for
+ *   bit. zero_std_to_one != 0: a standard deviation of 0 counts as 1 (MONAI's rule); otherwise the division is IEEE (n == 1 with
+ *   ddof == 1: NaN, as torch). n == 0 copies the channel. n int32 [c]. scratch: c * MI355_ZSCORE_SELECT_SCRATCH_BYTES bytes, every word
+ *   written before it is read. Three launches.
+ * mi355_threshold_any: out[v] = 1 if x[ch][v] > thr[ch] for any channel, else 0 (uint8 [voxels]; thr DEVICE float[c]). One launch. */
+#define MI355_PERCENTILE_MAX_Q 4
+#define MI355_PERCENTILE_SCRATCH_BYTES 32896
+#define MI355_ZSCORE_SELECT_SCRATCH_BYTES 20512
+#define MI355_WINDOW_CLAMP 0
+#define MI355_WINDOW_RESCALE 1
+#define MI355_WINDOW_SHIFT_FLOOR 2
+#define MI355_SELECT_ALL 0
+#define MI355_SELECT_NONZERO 1
+#define MI355_SELECT_ABS_ABOVE 2
+int mi355_percentiles(const float* x, int32_t c, int64_t voxels, const double* q, int32_t nq, const float* above, float* out, float* ranks,
+                      int32_t* n, void* scratch, void* stream);
+int mi355_window(const float* x, int32_t x_channels, float* y, int32_t c, int64_t voxels, const float* lo, const float* hi, int32_t mode,
+                 float floor, float ceiling, void* stream);
+int mi355_zscore_select(const float* x, float* y, int32_t c, int64_t voxels, int32_t select, float threshold, int32_t center, int32_t ddof,
+                        int32_t zero_std_to_one, int32_t* n, void* scratch, void* stream);
+int mi355_threshold_any(const float* x, int32_t c, int64_t voxels, const float* thr, uint8_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
