@@ -84,7 +84,7 @@ class HipNetBase(nn.Module):
         """list(self.parameters()), cached while the module tree is unchanged (see _TREE_EPOCH; conversions that replace Parameter
         objects -- .to_empty(), overwrite-on-conversion -- go through _apply, deletions through __delattr__)."""
         c = self.__dict__.get("_params_cache")
-        if c is None or c[0] != _TREE_EPOCH[0] or not _ops.HOST_CACHES:
+        if c is None or c[0] != _TREE_EPOCH[0]:
             c = self.__dict__["_params_cache"] = (_TREE_EPOCH[0], list(self.parameters()))
         return list(c[1])
 
@@ -180,12 +180,11 @@ class HipNetBase(nn.Module):
         launches during the step. Entries whose weight moved, or whose pack source is a transformed copy (ConvTranspose3d(k2, s2) as a
         1x1x1 GEMM), are dropped and rebuilt lazily as before."""
         batch = []
-        single = os.environ.get("MI355_BATCH_PACK", "1") == "0"      # A/B switch: the former one-launch-per-pack behaviour
         for p in self._params():
             ent = self._packed.get(id(p))
             if ent is None or not (force or ent[0] != p._version):
                 continue
-            if single or ent[3] or ent[2] != p.data_ptr():
+            if ent[3] or ent[2] != p.data_ptr():
                 del self._packed[id(p)]
                 continue
             ent[0] = p._version
@@ -270,7 +269,7 @@ class HipNetBase(nn.Module):
         """id(parameter) -> its slice of the gradient buffer `gbuf`, shaped like the parameter. The views of the engine's own flat
         gradient buffer are made once and kept (two torch calls per parameter and backward otherwise: ~0.4 ms of host time per step);
         a scratch buffer of an accumulating backward gets fresh ones."""
-        own = gbuf is self._flat_grad and _ops.HOST_CACHES
+        own = gbuf is self._flat_grad
         c = self.__dict__.get("_gview_cache")
         if own and c is not None and c[0] is gbuf and c[1] == _TREE_EPOCH[0] and c[2] is self._offsets:
             return c[3]

@@ -18,10 +18,6 @@ from ._lib import (IN_AFFINE_ACT, IN_PLAIN, IN_S2D, IN_ZERO_INSERT, OUT_D2S, OUT
                    W_PACKED, W_PACKED_F32_NARROW, MiAct, MiConvDesc, MiDiceOpts, MiFocalOpts, MiGnBwdFuse, MiTverskyOpts, check)
 
 
-# MI355_HOST_CACHES=0: the per-call forms of round 4 (descriptors, the Winograd routing query, the engine's parameter list and gradient
-# views rebuilt every time) -- the A/B switch of the host-enqueue measurement (tools/host_enqueue.py, profiles/r5_host_enqueue.txt)
-HOST_CACHES = os.environ.get("MI355_HOST_CACHES", "1") != "0"
-
 # Profiler families (Backend.prof names; bench.py's roofline rows and PMC_FAMILY key on them) of the kernels mi355_conv3d_fwd_config /
 # mi355_conv3d_wgrad_config name, by name prefix; any other kernel is a family of its own. A weight-gradient family adds " (+reduce)".
 PROF_FAMILIES = (("conv3d_k3_bf16<", "conv3d_k3_bf16<...>"), ("conv3d_k3_lp_zring", "conv3d_k3_bf16<...>"), ("conv3d_c4_fwd", "conv3d_c4_fwd"),
@@ -30,6 +26,20 @@ PROF_FAMILIES = (("conv3d_k3_bf16<", "conv3d_k3_bf16<...>"), ("conv3d_k3_lp_zrin
 
 def prof_family(kernel):
     return next((family for prefix, family in PROF_FAMILIES if kernel.startswith(prefix)), kernel)
+
+
+def conv_cost(x, y, kd, out_dhw=None, in_mode=IN_PLAIN, out_mode=OUT_PLAIN, elem=None):
+    """(algorithmic flops, unfused-compulsory bytes [SURVEY 8d: input + output + weights once], bytes of the output) of a conv between the
+    views x and y -- a weight gradient passes (x, dy) -- that computes `out_dhw` voxels per sample (None: y's). elem: bytes per element
+    of (x, y); None: algorithmic bytes follow the storage types."""
+    out_dhw = y.shape[1:4] if out_dhw is None else out_dhw
+    nvox = x.shape[0] * out_dhw[0] * out_dhw[1] * out_dhw[2]
+    flops = 2.0 * nvox * x.c * y.c * kd ** 3 * (8 if (in_mode == IN_S2D or out_mode == OUT_D2S) else 1)
+    if in_mode == IN_ZERO_INSERT:
+        flops /= 8.0   # algorithmic work of a stride-2 transposed conv: 27/8 taps per output voxel on average
+    xb, yb = elem or (x.buf.element_size(), y.buf.element_size())
+    ybytes = float(yb) * nvox * y.c
+    return flops, xb * (x.shape[0] * x.shape[1] * x.shape[2] * x.shape[3] * x.c) + ybytes + 4.0 * kd ** 3 * x.c * y.c, ybytes
 
 
 ACT_DTYPES = {torch.float32: _lib.ACT_F32, torch.bfloat16: _lib.ACT_BF16, torch.float16: _lib.ACT_F16}      # storage types of an activation view
@@ -68,9 +78,11 @@ class Act:
         return self.buf.data_ptr() + self.buf.element_size() * self.c0
 
     def desc(self):
-        """The view's mi355_act, built once (buf / c0 / c are fixed at construction; the library only reads the struct)."""
+        """The view's mi355_act, built once (buf / c0 / c are fixed at construction; the library only reads the struct). One of the host-side
+        caches measured in profiles/r5_host_enqueue.txt, with the routing answers of Backend._asked_once and the engine's parameter list
+        and gradient views."""
         d_ = self._d
-        if d_ is None or not HOST_CACHES:
+        if d_ is None:
             n, d, h, w, ld = self.buf.shape
             d_ = self._d = MiAct(self.ptr(), n, d, h, w, self.c, ld, ACT_DTYPES[self.buf.dtype])
         return d_
@@ -90,8 +102,7 @@ def _p(t):
     return None if t is None else t.data_ptr()
 
 
-_current_raw_stream = ((os.environ.get("MI355_RAW_STREAM", "1") != "0" and getattr(torch._C, "_cuda_getCurrentRawStream", None))
-                       or (lambda i: torch.cuda.current_stream(i).cuda_stream))
+_current_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None) or (lambda i: torch.cuda.current_stream(i).cuda_stream)
 
 
 class PackedWeight:
@@ -161,8 +172,8 @@ class PackedWeight:
 
 
 class Backend:
-    # Routing threshold of the Winograd kernels (voxels per sample). The first, 4-wave form showed no gain on the 16^3 level (256 channels:
-    # profiles/r2_winograd_prep_measurement.txt, r3_winograd_landing.txt); the 8-wave kernel and the interleaved ring weight gradient do
+    # Routing threshold of the Winograd kernels, forward / dgrad and weight gradient alike (voxels per sample). The first, 4-wave form showed
+    # no gain on the 16^3 level (256 channels: profiles/r2_winograd_prep_measurement.txt, r3_winograd_landing.txt); the 8-wave kernel and the interleaved ring weight gradient do
     # (profiles/r3_wino_forms.txt section 5: forward 0.231 -> 0.136 ms, weight gradient 0.338 -> 0.220 ms, step 57.5 -> 56.0 ms). Below
     # 16^3 a launch has fewer workgroups than the chip has CUs: the direct kernels' smaller tiles stay.
     WINO_MIN_VOXELS = 16 ** 3
@@ -202,19 +213,34 @@ class Backend:
         # (A first Winograd weight gradient -- one dz per workgroup, planes transformed three times -- measured 2x SLOWER than the ring
         # kernel, profiles/r3_winograd_landing.txt, and was deleted.)
         self.wgrad_form = os.environ.get("MI355_WGRAD_FORM", "wino")
-        if os.environ.get("MI355_WINO_MIN_VOXELS"):          # A/B of the routing threshold (forward / dgrad and weight gradient alike)
-            self.WINO_MIN_VOXELS = int(os.environ["MI355_WINO_MIN_VOXELS"])
 
         # set to a list to collect one record per conv launch: (kernel family, flops, unfused-compulsory bytes [SURVEY 8d: inputs + outputs +
         # weights once], start event, end event, instantiation [the name a rocprofv3 trace shows, or None], bytes of the reads the
-        # launch FUSES on top of the compulsory ones [residual, normalised tensor of the norm-backward sums]) -- see _prof_add
+        # launch FUSES on top of the compulsory ones [residual, normalised tensor of the norm-backward sums]) -- see _timed
         self.prof = None
         # norm statistics leave with the producing conv's epilogue (csrc/gn_fuse.h). False: every statistic is a standalone pass
         # over the tensor again (the round-1 form; kept as the cross-check of the fused path, tests/test_ops_gpu.py)
         self.fused_stats = os.environ.get("MI355_FUSED_STATS", "1") != "0"
 
-    def _prof_add(self, name, flops, byts, e0, e1, variant=None, fused_bytes=0.0):
-        self.prof.append((name, flops, byts, e0, e1, variant, fused_bytes))
+    def _timed(self, launch, what, row):
+        """check(launch(), what) -- every conv launch. While `prof` is a list: between two HIP events on the launch stream, and the record
+        of this one kernel is appended; row() answers its (family, flops, bytes, variant, fused bytes) and is not called otherwise."""
+        if self.prof is None:
+            return check(launch(), what)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        check(launch(), what)
+        e1.record()
+        family, flops, byts, variant, fused_bytes = row()
+        self.prof.append((family, flops, byts, e0, e1, variant, fused_bytes))
+
+    @staticmethod
+    def _asked_once(answers, key, ask):
+        """The library's yes / no to a call signature `key`, asked (ask()) the first time the signature is seen and kept in `answers`."""
+        ok = answers.get(key)
+        if ok is None:
+            ok = answers[key] = bool(ask())
+        return ok
 
     def set_precision(self, name):
         """"fp32" (exact f32 MFMA, default) | "bf16x3" | "bf16x6" (split-bf16 fp32 emulation) | "bf16" | "fp16" (mixed precision: operands
@@ -359,9 +385,6 @@ class Backend:
         (mean_rstd, scale, shift) of gx: have the epilogue emit the first pass of gn_act_bwd. Returns None, or (records, B) to
         hand to gn_act_bwd(partials=...)."""
         pad = kd // 2 if pad is None else pad
-        self._same_storage("conv_fwd: residual", residual, y, "y")
-        if gnb is not None:
-            self._same_storage("conv_fwd: normalised tensor of the norm-backward sums", gnb[0], y, "y")
         if out_dhw is None:
             out_dhw = x.shape[1:4] if out_mode == OUT_D2S else y.shape[1:4]
         if (self.winograd and self.precision == PREC_F32 and kd == 3 and stride == 1 and pad == 1 and in_mode in (IN_PLAIN, IN_AFFINE_ACT)
@@ -377,14 +400,17 @@ class Backend:
                 form = "3d" if x.c >= 256 and (in_mode == IN_PLAIN or x.shape[1] * x.shape[2] * x.shape[3] <= 16 ** 3) else "2d"
             key = (x.shape, x.ld, x.dtype, x.ptr() & 15, y.c, y.ld, y.dtype, in_mode, slope, scale is None, shift is None,
                    None if residual is None else residual.ld, form)
-            ok = self._wino_ok.get(key) if HOST_CACHES else None
-            if ok is None:
+
+            def ask():
                 probe = self._desc(3, 1, 1, in_mode, slope, scale, shift, bias, residual, chscale, (0, 0, 0), y.shape[1:4], [], in_slope, OUT_PLAIN)
                 xd_, yd_ = x.desc(), y.desc()
                 supported = self.lib.mi355_conv3d_wino3d_supported if form == "3d" else self.lib.mi355_conv3d_wino_supported
-                ok = self._wino_ok[key] = bool(supported(ctypes.byref(xd_), ctypes.byref(yd_), ctypes.byref(probe)))
-            if ok:
+                return supported(ctypes.byref(xd_), ctypes.byref(yd_), ctypes.byref(probe))
+            if self._asked_once(self._wino_ok, key, ask):      # (conv_fwd_wino does the storage-type checks of its operands itself)
                 return self.conv_fwd_wino(x, wp.wino(form), y, in_mode, slope, scale, shift, bias, residual, chscale, in_slope, moments, gnb)
+        self._same_storage("conv_fwd: residual", residual, y, "y")
+        if gnb is not None:
+            self._same_storage("conv_fwd: normalised tensor of the norm-backward sums", gnb[0], y, "y")
         keep = []
         d = self._desc(kd, stride, pad, in_mode, slope, scale, shift, bias, residual, chscale, off, out_dhw, keep, in_slope, out_mode)
         xd, yd = x.desc(), y.desc()
@@ -392,52 +418,51 @@ class Backend:
         y.mom = None
         gparts = None
         if self.fused_stats and (moments or gnb is not None):
-            if gnb is not None and not moments:
+            if not moments:
                 # the query is for the norm-backward sums (a kernel may carry the moments epilogue but not this one): a placeholder
-                # marks the request, the real descriptor replaces it below
+                # marks the request, the real descriptor replaces it in _request_stats
                 probe = MiGnBwdFuse()
                 d.gn_bwd = ctypes.pointer(probe)
             nb = self.lib.mi355_conv3d_stats_blocks(ctypes.byref(xd), ctypes.byref(yd), ctypes.byref(d))
             d.gn_bwd = None
-            if nb > 0 and moments:
-                rec = torch.empty(x.shape[0], nb, y.c, 3, dtype=torch.float32, device=self.device)
-                d.moments_out = rec.data_ptr()
-                y.mom = [(rec, nb, y.c)]                      # folded after the launch (see below)
-            elif nb > 0 and in_mode == IN_PLAIN and d.wformat == W_PACKED:
-                gx, st, groups, gslope = gnb
-                assert gx.shape == y.shape
-                rec = torch.empty(x.shape[0], nb, y.c, 2, dtype=torch.float32, device=self.device)
-                fuse = MiGnBwdFuse(gx.ptr(), gx.ld, st[1].data_ptr(), st[2].data_ptr(), st[0].data_ptr(), groups, gslope, rec.data_ptr())
-                d.gn_bwd = ctypes.pointer(fuse)
-                keep.extend([fuse, gx, st])
-                gparts = (rec, nb)
-        if self.prof is None:
-            check(self.lib.mi355_conv3d_fwd(ctypes.byref(xd), wptr, ctypes.byref(yd), ctypes.byref(d), self.stream()), "conv3d_fwd")
-            return self._fold_after(y, gparts)
-        # profiling: HIP events on the launch stream around this one kernel, keyed by the kernel's trace name
-        name = ctypes.create_string_buffer(96)
-        self.lib.mi355_conv3d_fwd_config(ctypes.byref(xd), ctypes.byref(yd), ctypes.byref(d), name, 96)
-        kernel = name.value.decode()
-        family = prof_family(kernel)
-        variant = None
-        if family.endswith("<...>"):
-            # one family, several kernels: the row keeps the instantiation this call launches, named exactly as a rocprofv3 trace prints it
-            variant = kernel
-            if os.environ.get("MI355_PROF_SHAPES") == "1":      # developer aid: one row per layer shape (tools/r6_call.sh)
-                variant += f" [{x.c}->{y.c} @{out_dhw[0]} x{x.shape[0]}]"
-        nvox = x.shape[0] * out_dhw[0] * out_dhw[1] * out_dhw[2]
-        flops = 2.0 * nvox * x.c * y.c * kd ** 3 * (8 if (in_mode == IN_S2D or out_mode == OUT_D2S) else 1)
-        if in_mode == IN_ZERO_INSERT:
-            flops /= 8.0   # algorithmic work of a stride-2 transposed conv: 27/8 taps per output voxel on average
-        xb, yb = x.buf.element_size(), y.buf.element_size()          # algorithmic bytes follow the storage types
-        byts = xb * (x.shape[0] * x.shape[1] * x.shape[2] * x.shape[3] * x.c) + yb * nvox * y.c + 4.0 * kd ** 3 * x.c * y.c
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        check(self.lib.mi355_conv3d_fwd(ctypes.byref(xd), wptr, ctypes.byref(yd), ctypes.byref(d), self.stream()), "conv3d_fwd")
-        e1.record()
-        fused = float(yb) * nvox * y.c * ((residual is not None) + (gparts is not None))
-        self._prof_add(family, flops, byts, e0, e1, variant, fused)
+            if nb > 0:
+                gparts = self._request_stats(x, y, d, keep, nb, moments, gnb, in_mode == IN_PLAIN and d.wformat == W_PACKED)
+
+        def row():      # keyed by the kernel's trace name
+            name = ctypes.create_string_buffer(96)
+            self.lib.mi355_conv3d_fwd_config(ctypes.byref(xd), ctypes.byref(yd), ctypes.byref(d), name, 96)
+            kernel = name.value.decode()
+            family = prof_family(kernel)
+            variant = None
+            if family.endswith("<...>"):
+                # one family, several kernels: the row keeps the instantiation this call launches, named exactly as a rocprofv3 trace prints it
+                variant = kernel
+                if os.environ.get("MI355_PROF_SHAPES") == "1":      # developer aid: one row per layer shape (tools/r6_call.sh)
+                    variant += f" [{x.c}->{y.c} @{out_dhw[0]} x{x.shape[0]}]"
+            flops, byts, ybytes = conv_cost(x, y, kd, out_dhw, in_mode, out_mode)
+            return family, flops, byts, variant, ybytes * ((residual is not None) + (gparts is not None))
+        self._timed(lambda: self.lib.mi355_conv3d_fwd(ctypes.byref(xd), wptr, ctypes.byref(yd), ctypes.byref(d), self.stream()), "conv3d_fwd", row)
         return self._fold_after(y, gparts)
+
+    def _request_stats(self, x, y, d, keep, nb, moments, gnb, gnb_eligible):
+        """The statistics request of a conv launch whose epilogue leaves `nb` records per (sample, channel): the partial moments of y
+        (`moments`, which wins: d.moments_out, y.mom) or else, where the launch can (`gnb_eligible`), the first pass of gn_act_bwd over
+        gnb = (gx, stats, groups, slope) (d.gn_bwd). Returns None or the (records, nb) of the latter; both are folded after the launch
+        (_fold_after)."""
+        if moments:
+            rec = torch.empty(x.shape[0], nb, y.c, 3, dtype=torch.float32, device=self.device)
+            d.moments_out = rec.data_ptr()
+            y.mom = [(rec, nb, y.c)]
+            return None
+        if not gnb_eligible:
+            return None
+        gx, st, groups, gslope = gnb
+        assert gx.shape == y.shape
+        rec = torch.empty(x.shape[0], nb, y.c, 2, dtype=torch.float32, device=self.device)
+        fuse = MiGnBwdFuse(gx.ptr(), gx.ld, st[1].data_ptr(), st[2].data_ptr(), st[0].data_ptr(), groups, gslope, rec.data_ptr())
+        d.gn_bwd = ctypes.pointer(fuse)
+        keep.extend([fuse, gx, st])
+        return rec, nb
 
     # -- Winograd form of the 3x3x3 stride-1 conv (csrc/conv3d_wino.hip) -------------------------------------------------------------
     def wino_pack_weight(self, w, mode=0, form=None):
@@ -470,32 +495,18 @@ class Backend:
         y.mom = None
         gparts = None
         if self.fused_stats and (moments or gnb is not None):
-            nb = self.lib.mi355_conv3d_wino_stats_blocks(ctypes.byref(yd))
-            if moments:
-                rec = torch.empty(x.shape[0], nb, y.c, 3, dtype=torch.float32, device=self.device)
-                d.moments_out = rec.data_ptr()
-                y.mom = [(rec, nb, y.c)]
-            elif in_mode == IN_PLAIN:
-                gx, st, groups, gslope = gnb
-                rec = torch.empty(x.shape[0], nb, y.c, 2, dtype=torch.float32, device=self.device)
-                fuse = MiGnBwdFuse(gx.ptr(), gx.ld, st[1].data_ptr(), st[2].data_ptr(), st[0].data_ptr(), groups, gslope, rec.data_ptr())
-                d.gn_bwd = ctypes.pointer(fuse)
-                keep.extend([fuse, gx, st])
-                gparts = (rec, nb)
-        if self.prof is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
+            gparts = self._request_stats(x, y, d, keep, self.lib.mi355_conv3d_wino_stats_blocks(ctypes.byref(yd)), moments, gnb, in_mode == IN_PLAIN)
         form3 = getattr(up, "mi355_form", "2d") == "3d"
-        fwd = self.lib.mi355_conv3d_wino3d_fwd if form3 else self.lib.mi355_conv3d_wino_fwd
-        check(fwd(ctypes.byref(xd), up.data_ptr(), ctypes.byref(yd), ctypes.byref(d), self.stream()), "conv3d_wino3d_fwd" if form3 else "conv3d_wino_fwd")
-        if self.prof is not None:
-            e1.record()
-            nvox = y.shape[0] * y.shape[1] * y.shape[2] * y.shape[3]
+
+        def row():      # (fp32 tensors only: 4-byte elements)
+            flops, byts, ybytes = conv_cost(x, y, 3, elem=(4, 4))
             fuse = 1 if d.moments_out else (2 if gparts is not None else 0)
             kern = "conv3d_wino3d" if form3 else "conv3d_wino2d_d8"
-            self._prof_add("conv3d_wino3d" if form3 else "conv3d_wino2d", 2.0 * nvox * x.c * y.c * 27, 4.0 * (nvox * (x.c + y.c) + 27 * x.c * y.c), e0, e1,
-                           f"{kern}<{1 if in_mode == IN_AFFINE_ACT else 0}, {fuse}>",
-                           4.0 * nvox * y.c * ((residual is not None) + (gparts is not None)))
+            return ("conv3d_wino3d" if form3 else "conv3d_wino2d", flops, byts, f"{kern}<{1 if in_mode == IN_AFFINE_ACT else 0}, {fuse}>",
+                    ybytes * ((residual is not None) + (gparts is not None)))
+        fwd = self.lib.mi355_conv3d_wino3d_fwd if form3 else self.lib.mi355_conv3d_wino_fwd
+        self._timed(lambda: fwd(ctypes.byref(xd), up.data_ptr(), ctypes.byref(yd), ctypes.byref(d), self.stream()),
+                    "conv3d_wino3d_fwd" if form3 else "conv3d_wino_fwd", row)
         return self._fold_after(y, gparts)
 
     def _fold_after(self, y, gparts):
@@ -515,42 +526,30 @@ class Backend:
         d = self._desc(kd, stride, pad, in_mode, slope, scale, shift, None, None, None, (0, 0, 0),
                        x.shape[1:4] if out_mode == OUT_D2S else dy.shape[1:4], keep, in_slope, out_mode)
         xd, dyd = x.desc(), dy.desc()
+        args = (ctypes.byref(xd), ctypes.byref(dyd), ctypes.byref(d))
+        # the Winograd ring where the policy routes the layer and the library takes it (workspace 0: it does not), else the generic route
+        nbytes = 0
         if (self.wgrad_form == "wino" and self.precision == PREC_F32 and kd == 3 and stride == 1 and pad == 1 and in_mode in (IN_PLAIN, IN_AFFINE_ACT)
                 and out_mode == OUT_PLAIN and x.c >= 8 and dy.c >= 8 and x.shape[1] * x.shape[2] * x.shape[3] >= self.WINO_MIN_VOXELS):
-            nbytes = self.lib.mi355_conv3d_wgrad_wino_workspace(ctypes.byref(xd), ctypes.byref(dyd), ctypes.byref(d))
-            if nbytes:
-                ws = self.ws(nbytes)
-                assert dw.is_contiguous()
-                if self.prof is not None:
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record()
-                check(self.lib.mi355_conv3d_wgrad_wino(ctypes.byref(xd), ctypes.byref(dyd), dw.data_ptr(), ctypes.byref(d), ws.data_ptr(),
-                                                       ws.numel() * 4, self.stream()), "conv3d_wgrad_wino")
-                if self.prof is not None:
-                    e1.record()
-                    nvox = dy.shape[0] * dy.shape[1] * dy.shape[2] * dy.shape[3]
-                    self._prof_add("conv3d_wgrad_wino_ring (+reduce)", 2.0 * nvox * x.c * dy.c * 27,
-                                   4.0 * (nvox * (x.c + dy.c) + 27 * x.c * dy.c), e0, e1)
-                return
-        nbytes = self.lib.mi355_conv3d_wgrad_workspace(ctypes.byref(xd), ctypes.byref(dyd), ctypes.byref(d))
-        if nbytes == 0:
-            raise RuntimeError("conv3d_wgrad: unsupported configuration")
+            nbytes = self.lib.mi355_conv3d_wgrad_wino_workspace(*args)
+        if nbytes:
+            launch, what = self.lib.mi355_conv3d_wgrad_wino, "conv3d_wgrad_wino"
+
+            def row():
+                return ("conv3d_wgrad_wino_ring (+reduce)",) + conv_cost(x, dy, 3, elem=(4, 4))[:2] + (None, 0.0)
+        else:
+            nbytes = self.lib.mi355_conv3d_wgrad_workspace(*args)
+            if nbytes == 0:
+                raise RuntimeError("conv3d_wgrad: unsupported configuration")
+            launch, what = self.lib.mi355_conv3d_wgrad, "conv3d_wgrad"
+
+            def row():
+                name = ctypes.create_string_buffer(96)
+                self.lib.mi355_conv3d_wgrad_config(*args, name, 96)
+                return (prof_family(name.value.decode()) + " (+reduce)",) + conv_cost(x, dy, kd)[:2] + (None, 0.0)
         ws = self.ws(nbytes)
         assert dw.is_contiguous()
-        if self.prof is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        check(self.lib.mi355_conv3d_wgrad(ctypes.byref(xd), ctypes.byref(dyd), dw.data_ptr(), ctypes.byref(d), ws.data_ptr(),
-                                          ws.numel() * 4, self.stream()), "conv3d_wgrad")
-        if self.prof is not None:
-            e1.record()
-            nvox = dy.shape[0] * dy.shape[1] * dy.shape[2] * dy.shape[3]
-            flops = 2.0 * nvox * x.c * dy.c * kd ** 3
-            byts = (x.buf.element_size() * (x.shape[0] * x.shape[1] * x.shape[2] * x.shape[3] * x.c) + dy.buf.element_size() * nvox * dy.c +
-                    4.0 * kd ** 3 * x.c * dy.c)
-            name = ctypes.create_string_buffer(96)
-            self.lib.mi355_conv3d_wgrad_config(ctypes.byref(xd), ctypes.byref(dyd), ctypes.byref(d), name, 96)
-            self._prof_add(prof_family(name.value.decode()) + " (+reduce)", flops, byts, e0, e1)
+        self._timed(lambda: launch(args[0], args[1], dw.data_ptr(), args[2], ws.data_ptr(), ws.numel() * 4, self.stream()), what, row)
 
     # -- first-layer backward in one pass over dy (csrc/conv3d_c4_bwd.hip) -----------------------------------------------------------------
     def c4_bwd_supported(self, x, dy, in_mode=IN_AFFINE_ACT, slope=0.0, scale=None, shift=None, in_slope=None):
@@ -559,12 +558,12 @@ class Backend:
             return False
         # asked once per call signature, like _wino_ok (mi355_conv3d_c4_bwd checks the same conditions again on every call)
         key = (x.shape, x.ld, x.dtype, x.ptr() & 15, dy.shape, dy.ld, dy.dtype, dy.ptr() & 15, in_mode, slope, scale is None, shift is None)
-        ok = self._c4_bwd_ok.get(key) if HOST_CACHES else None
-        if ok is None:
+
+        def ask():
             d = self._desc(3, 1, 1, in_mode, slope, scale, shift, None, None, None, (0, 0, 0), dy.shape[1:4], [], in_slope, OUT_PLAIN)
             xd, dyd = x.desc(), dy.desc()
-            ok = self._c4_bwd_ok[key] = bool(self.lib.mi355_conv3d_c4_bwd_supported(ctypes.byref(xd), ctypes.byref(dyd), ctypes.byref(d)))
-        return ok
+            return self.lib.mi355_conv3d_c4_bwd_supported(ctypes.byref(xd), ctypes.byref(dyd), ctypes.byref(d))
+        return self._asked_once(self._c4_bwd_ok, key, ask)
 
     def c4_bwd(self, x, dy, wp, dw, groups, gamma, mean_rstd, scale, shift, dgamma, dbeta, slope=0.0, in_slope=None):
         """Backward of [GroupNorm(4 channels) -> act -> Conv3d(4 -> 32, k3)] whose input needs no gradient: dw (OIDHW) and dgamma / dbeta in
@@ -579,17 +578,14 @@ class Backend:
         rec = torch.empty(x.shape[0], nb, 4, 2, dtype=torch.float32, device=self.device)
         ws = self.ws(max(nbytes, self.lib.mi355_gn_workspace(ctypes.byref(xd))))
         assert dw.is_contiguous()
-        if self.prof is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        check(self.lib.mi355_conv3d_c4_bwd(ctypes.byref(xd), ctypes.byref(dyd), wp.f32().data_ptr(), dw.data_ptr(), ctypes.byref(d),
-                                           mean_rstd.data_ptr(), groups, rec.data_ptr(), ws.data_ptr(), ws.numel() * 4, self.stream()), "conv3d_c4_bwd")
-        if self.prof is not None:
-            e1.record()
-            nvox = dy.shape[0] * dy.shape[1] * dy.shape[2] * dy.shape[3]
+
+        def row():
             # the two passes it replaces (weight gradient + data gradient, SURVEY 8d: each x + dy + w once): 2 x the forward's flops and
-            # algorithmic bytes -- the fused kernel MOVES half of those bytes (dy and x once), which is the point
-            self._prof_add("conv3d_c4_bwd (+reduce)", 2 * 2.0 * nvox * 4 * 32 * 27, 2 * 4.0 * (nvox * (4 + 32) + 27 * 4 * 32), e0, e1)
+            # algorithmic bytes (4-byte elements) -- the fused kernel MOVES half of those bytes (dy and x once), which is the point
+            flops, byts, _ = conv_cost(x, dy, 3, elem=(4, 4))
+            return "conv3d_c4_bwd (+reduce)", 2 * flops, 2 * byts, None, 0.0
+        self._timed(lambda: self.lib.mi355_conv3d_c4_bwd(ctypes.byref(xd), ctypes.byref(dyd), wp.f32().data_ptr(), dw.data_ptr(), ctypes.byref(d), mean_rstd.data_ptr(),
+                                                         groups, rec.data_ptr(), ws.data_ptr(), ws.numel() * 4, self.stream()), "conv3d_c4_bwd", row)
         # the records are few (<= ~1024 per sample): finalised in place of the norm backward's first pass; dgamma / dbeta only
         check(self.lib.mi355_gn_bwd_params(ctypes.byref(xd), groups, _p(gamma), mean_rstd.data_ptr(), _p(dgamma), _p(dbeta), rec.data_ptr(), nb,
                                            ws.data_ptr(), ws.numel() * 4, self.stream()), "gn_bwd_params")
