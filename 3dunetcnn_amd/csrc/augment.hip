@@ -6,13 +6,14 @@
 //         lanes of a slightly rotated row share cache lines) and walks the brick's 16 z. Per voxel the map M_n is evaluated once; the
 //         image channels are blended from it (trilinear), the label channels picked (nearest, round half to even). With `normalize` it
 //         leaves one (sum, sum of squares) record per (brick, channel) of the values it wrote, shifted by K = the channel's first SOURCE
-//         voxel (as mi355_zscore shifts by the first voxel: the fp32 sums then carry deviations, not the level).
+//         voxel (shifted_mean_rstd of volume_common.h: the fp32 sums then carry deviations, not the level).
 //  pass B (augment_finalize_kernel): every workgroup folds the records of its (sample, channel) in one fixed order (fp64), then applies
 //         (x - mean) * rstd * gain + offset in place with 16-byte accesses.
 //  No atomics anywhere: two runs give the same bits. Without `normalize` pass B does not run: gain and offset (if given) go into pass A's
 //  store. A map whose coordinates are integers (flips, crops, identity) copies source voxels bit for bit.
 #include "gfx950_dialect.h"
 #include "../../include/mi355_unet3d.h"
+#include "volume_common.h"
 
 #define AUG_BX 64
 #define AUG_BY 4
@@ -31,9 +32,6 @@ struct AugArgs {
   int nbx, nby, nbz;
   int padding, normalize;
 };
-
-__device__ __forceinline__ int aug_clampi(int v, int hi) { return v < 0 ? 0 : (v < hi ? v : hi - 1); }
-__device__ __forceinline__ float aug_clampf(float v, float hi) { return v < 0.f ? 0.f : (v > hi ? hi : v); }
 
 __global__ __launch_bounds__(AUG_BX * AUG_BY) void augment_resample_kernel(AugArgs a) {
   __shared__ float red[AUG_BY][AUG_CG][2];
@@ -76,10 +74,8 @@ __global__ __launch_bounds__(AUG_BX * AUG_BY) void augment_resample_kernel(AugAr
         const size_t v = ((size_t)z * a.dh + y) * a.dw + x;
         if (g == 0 && a.lbl) {
           // labels: the nearest source voxel of the same coordinates (rintf: half to even)
-          int iz = (int)rintf(cz0), iy = (int)rintf(cy0), ix = (int)rintf(cx0);
-          const bool inside = iz >= 0 && iy >= 0 && ix >= 0 && iz < a.sd && iy < a.sh && ix < a.sw;
-          iz = aug_clampi(iz, a.sd); iy = aug_clampi(iy, a.sh); ix = aug_clampi(ix, a.sw);
-          const size_t o = ((size_t)iz * a.sh + iy) * a.sw + ix;
+          bool inside;
+          const size_t o = nearest_source(cz0, cy0, cx0, false, a.sd, a.sh, a.sw, inside);
           const bool zero = a.padding == 1 && !inside;
           if (a.lbl_f32) {
             const float* ls = (const float*)a.lbl + (size_t)n * a.cl * SV; float* ld = (float*)a.lbl_out + (size_t)n * a.cl * DV;
@@ -90,10 +86,8 @@ __global__ __launch_bounds__(AUG_BX * AUG_BY) void augment_resample_kernel(AugAr
             for (int c = 0; c < a.cl; ++c) ld[(size_t)c * DV + v] = zero ? (unsigned char)0 : ls[(size_t)c * SV + o];
           }
         }
-        float cz = cz0, cy = cy0, cx = cx0;
-        if (a.padding == 0) {
-          cz = aug_clampf(cz, (float)(a.sd - 1)); cy = aug_clampf(cy, (float)(a.sh - 1)); cx = aug_clampf(cx, (float)(a.sw - 1));
-        }
+        float cz = cz0, cy = cy0, cx = cx0;           // trilinear_setup of volume_common.h written out: see there (the helper costs eight VGPRs here)
+        if (a.padding == 0) { cz = clamp_coord(cz, (float)(a.sd - 1)); cy = clamp_coord(cy, (float)(a.sh - 1)); cx = clamp_coord(cx, (float)(a.sw - 1)); }
         const float fz = floorf(cz), fy = floorf(cy), fx = floorf(cx);
         const float lz = cz - fz, ly = cy - fy, lx = cx - fx;
         const int iz0 = (int)fz, iy0 = (int)fy, ix0 = (int)fx;
@@ -107,23 +101,16 @@ __global__ __launch_bounds__(AUG_BX * AUG_BY) void augment_resample_kernel(AugAr
           const bool inside = iz >= 0 && iy >= 0 && ix >= 0 && iz < a.sd && iy < a.sh && ix < a.sw;
           if (!inside) {
             if (a.padding == 1) w = 0.f;           // zeros outside; with border padding the clamp above leaves only weight-0 corners outside
-            iz = aug_clampi(iz, a.sd); iy = aug_clampi(iy, a.sh); ix = aug_clampi(ix, a.sw);
+            iz = clamp_index(iz, a.sd); iy = clamp_index(iy, a.sh); ix = clamp_index(ix, a.sw);
           }
           wgt[q] = w; off[q] = ((size_t)iz * a.sh + iy) * a.sw + ix;
         }
 #pragma unroll
         for (int j = 0; j < AUG_CG; ++j) {
           if (c0 + j >= a.ci) continue;
-          const float* s = sc[j];
           float val;
-          if (exact) {
-            val = wgt[0] != 0.f ? s[off[0]] : 0.f;
-          } else {
-            // x pairs first, then y, then z (the order of resample_affine_kernel)
-            const float v00 = wgt[0] * s[off[0]] + wgt[1] * s[off[1]], v01 = wgt[2] * s[off[2]] + wgt[3] * s[off[3]];
-            const float v10 = wgt[4] * s[off[4]] + wgt[5] * s[off[5]], v11 = wgt[6] * s[off[6]] + wgt[7] * s[off[7]];
-            val = (v00 + v01) + (v10 + v11);
-          }
+          if (exact) val = wgt[0] != 0.f ? sc[j][off[0]] : 0.f;
+          else val = trilinear_blend(sc[j], wgt, off);
           const float t = val - K[j];
           s0[j] += t; s1[j] += t * t;
           dc[j][v] = affine ? val * ga[j] + of[j] : val;
@@ -159,21 +146,8 @@ __global__ __launch_bounds__(AUG_B_THREADS) void augment_finalize_kernel(float* 
   const float* r = rec + (size_t)nc * nrec * 2;
   double a0 = 0.0, a1 = 0.0;
   for (int i = t; i < nrec; i += AUG_B_THREADS) { a0 += (double)r[2 * i]; a1 += (double)r[2 * i + 1]; }
-  r0[t] = a0; r1[t] = a1;
-  __syncthreads();
-  for (int s = AUG_B_THREADS / 2; s > 0; s >>= 1) {
-    if (t < s) { r0[t] += r0[t + s]; r1[t] += r1[t + s]; }
-    __syncthreads();
-  }
-  if (t == 0) {
-    const double K = (double)img[(size_t)nc * SV];
-    const double mean = K + r0[0] / (double)DV;
-    double var = (r1[0] - r0[0] * r0[0] / (double)DV) / (double)DV;    // population variance (torch.std(unbiased=False))
-    if (var < 0.0) var = 0.0;
-    double sd = sqrt(var);
-    if (sd == 0.0) sd = 1.0;                                            // MONAI NormalizeIntensity: divisor 0 -> 1
-    stat[0] = (float)mean; stat[1] = (float)(1.0 / sd);
-  }
+  block_sum_256(r0, r1, a0, a1);
+  if (t == 0) shifted_mean_rstd((double)img[(size_t)nc * SV], r0[0], r1[0], (double)DV, stat[0], stat[1]);
   __syncthreads();
   const float mean = stat[0];
   const float sc = stat[1] * (gain ? gain[nc] : 1.f), of = offset ? offset[nc] : 0.f;

@@ -35,13 +35,13 @@
 // global atomicAdd per (workgroup, label).
 #include "gfx950_dialect.h"
 #include "../../include/mi355_unet3d.h"
+#include "volume_common.h"
 
 #define CC_TX 64
 #define CC_TY 4
 #define CC_TZ 4
 #define CC_ROWS (CC_TY * CC_TZ)
 #define CC_TILE (CC_TX * CC_ROWS)
-#define CC_MAX_VOXELS 2147483646ll          // labels are 1 + index in int32
 #define CC_HASH 1024                        // slots of the per-workgroup size table: a workgroup inserts at most 512 runs
 
 #ifdef MI355_EMU
@@ -51,8 +51,6 @@ static inline int ld_lds(const int* p) { return __atomic_load_n(p, __ATOMIC_RELA
 __device__ __forceinline__ int ld_agent(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ int ld_lds(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 #endif
-
-static inline unsigned cc_blocks(long long n, int per_block) { return (unsigned)((n + per_block - 1) / per_block); }
 
 // ---- a. ensemble mean + threshold -------------------------------------------------------------------------------------------------
 __global__ void ensemble_threshold_kernel(const float* probs, int M, long long n, float thr, float* mean, unsigned char* mask, int vec) {
@@ -222,24 +220,18 @@ __global__ void __launch_bounds__(256) cc_flatten_kernel(long long V, int* label
   L[vv] = a;
 }
 
-static int cc_check_dims(int32_t c, int32_t d, int32_t h, int32_t w) {
-  if (c < 1 || c > 65535 || d < 1 || h < 1 || w < 1) return MI355_EINVAL;
-  if ((long long)d * h * w > CC_MAX_VOXELS) return MI355_EINVAL;
-  return MI355_OK;
-}
-
 extern "C" int mi355_cc_label(const uint8_t* mask, int32_t c, int32_t d, int32_t h, int32_t w, int32_t connectivity, int32_t* labels,
                               void* stream) {
   if (!mask || !labels || (connectivity != 6 && connectivity != 26)) return MI355_EINVAL;
-  int rc = cc_check_dims(c, d, h, w); if (rc) return rc;
+  int rc = vol_check_dims(c, d, h, w); if (rc) return rc;
   const long long V = (long long)d * h * w;
   const int tiles_x = ceil_div(w, CC_TX), tiles_y = ceil_div(h, CC_TY), tiles_z = ceil_div(d, CC_TZ), conn26 = connectivity == 26;
   LAUNCH(cc_local_kernel, dim3((unsigned)((long long)tiles_x * tiles_y * tiles_z), c), dim3(256), 0, stream, (const unsigned char*)mask,
          (int)d, (int)h, (int)w, tiles_x, tiles_y, conn26, (int*)labels);
   rc = LAUNCH_CHECK(); if (rc) return rc;
-  LAUNCH(cc_merge_kernel, dim3(cc_blocks(V, 256), c), dim3(256), 0, stream, (int)d, (int)h, (int)w, conn26, (int*)labels);
+  LAUNCH(cc_merge_kernel, dim3(vol_blocks(V, 256), c), dim3(256), 0, stream, (int)d, (int)h, (int)w, conn26, (int*)labels);
   rc = LAUNCH_CHECK(); if (rc) return rc;
-  LAUNCH(cc_flatten_kernel, dim3(cc_blocks(V, 256), c), dim3(256), 0, stream, V, (int*)labels);
+  LAUNCH(cc_flatten_kernel, dim3(vol_blocks(V, 256), c), dim3(256), 0, stream, V, (int*)labels);
   return LAUNCH_CHECK();
 }
 
@@ -248,7 +240,7 @@ extern "C" int mi355_cc_label(const uint8_t* mask, int32_t c, int32_t d, int32_t
 // [c][V] sizes (only the words at roots are ever touched)
 static size_t cc_small_bytes(int32_t c) { return (size_t)c * 8 + (((size_t)c * 4 + 7) & ~(size_t)7); }
 extern "C" size_t mi355_cc_workspace(int32_t c, int32_t d, int32_t h, int32_t w) {
-  if (cc_check_dims(c, d, h, w)) return 0;
+  if (vol_check_dims(c, d, h, w)) return 0;
   return cc_small_bytes(c) + (size_t)c * d * h * w * 4;
 }
 
@@ -343,22 +335,22 @@ __global__ void __launch_bounds__(256) cc_write_kernel(const unsigned char* mask
 extern "C" int mi355_cc_filter(const uint8_t* mask, const int32_t* labels, int32_t c, int32_t d, int32_t h, int32_t w, int32_t keep_largest,
                                int64_t min_size, uint8_t* out, int32_t* stats, void* ws, size_t ws_bytes, void* stream) {
   if (!mask || !labels || !out || !ws) return MI355_EINVAL;
-  int rc = cc_check_dims(c, d, h, w); if (rc) return rc;
+  int rc = vol_check_dims(c, d, h, w); if (rc) return rc;
   if (ws_bytes < mi355_cc_workspace(c, d, h, w)) return MI355_EWORKSPACE;
   const long long V = (long long)d * h * w;
   unsigned long long* best = (unsigned long long*)ws;
   int* count = (int*)((char*)ws + (size_t)c * 8);
   int* sizes = (int*)((char*)ws + cc_small_bytes(c));
   const int* L = (const int*)labels;
-  LAUNCH(cc_zero_kernel, dim3(cc_blocks(c, 256)), dim3(256), 0, stream, best, count, (int)c);
+  LAUNCH(cc_zero_kernel, dim3(vol_blocks(c, 256)), dim3(256), 0, stream, best, count, (int)c);
   rc = LAUNCH_CHECK(); if (rc) return rc;
-  LAUNCH(cc_roots_kernel, dim3(cc_blocks(V, 256), c), dim3(256), 0, stream, L, V, sizes);
+  LAUNCH(cc_roots_kernel, dim3(vol_blocks(V, 256), c), dim3(256), 0, stream, L, V, sizes);
   rc = LAUNCH_CHECK(); if (rc) return rc;
-  LAUNCH(cc_sizes_kernel, dim3(cc_blocks(V, 1024), c), dim3(256), 0, stream, L, V, sizes);
+  LAUNCH(cc_sizes_kernel, dim3(vol_blocks(V, 1024), c), dim3(256), 0, stream, L, V, sizes);
   rc = LAUNCH_CHECK(); if (rc) return rc;
-  LAUNCH(cc_select_kernel, dim3(cc_blocks(V, 1024), c), dim3(256), 0, stream, L, V, (const int*)sizes, best, count);
+  LAUNCH(cc_select_kernel, dim3(vol_blocks(V, 1024), c), dim3(256), 0, stream, L, V, (const int*)sizes, best, count);
   rc = LAUNCH_CHECK(); if (rc) return rc;
-  LAUNCH(cc_write_kernel, dim3(cc_blocks(V, 256), c), dim3(256), 0, stream, (const unsigned char*)mask, L, V, (const int*)sizes,
+  LAUNCH(cc_write_kernel, dim3(vol_blocks(V, 256), c), dim3(256), 0, stream, (const unsigned char*)mask, L, V, (const int*)sizes,
          (const unsigned long long*)best, (const int*)count, (int)keep_largest, (long long)min_size, (unsigned char*)out, (int*)stats);
   return LAUNCH_CHECK();
 }

@@ -1,11 +1,9 @@
 // Intensity normalisation on the device: exact per-channel percentiles of a dense, signed fp32 volume, the three window forms built on
 // them (clamp, rescale, shift-and-floor), the z-score over a selected set of voxels, and the any-channel threshold mask.
 //
-// The rules of metrics.hip hold here too. Every buffer is the caller's and has a closed-form size; everything is enqueued on `stream`;
-// NO WORKGROUP EVER WAITS FOR ANOTHER; no allocation, copy or host wait; a fixed number of launches whatever the data: percentiles 10,
-// window 1, zscore_select 3, threshold_any 1. Workgroups meet only in INTEGER atomics (histogram bins, the NaN counter), whose result does
-// not depend on arrival order. Floating sums are never accumulated atomically: a workgroup adds its own voxels in a fixed order into
-// doubles, stores the partials in its own slots, and one thread adds the slots in index order -- two calls give the same bits.
+// The rules at the top of volume_common.h hold. Every buffer is the caller's and has a closed-form size; everything is enqueued on
+// `stream`; a fixed number of launches whatever the data: percentiles 10, window 1, zscore_select 3, threshold_any 1. The integer atomics
+// are the histogram bins and the NaN counter; the floating sums are per-workgroup doubles that one thread adds in index order.
 //
 //   percentiles   radix select over the ORDER-PRESERVING KEY of the fp32 bit pattern (negatives: all bits flipped, the others: the sign
 //                 bit flipped; unsigned key order = value order, -0 just below +0, -NaN below -inf, +NaN above +inf): 4 passes of 8 bits
@@ -25,8 +23,9 @@
 //                 which forms (x - mean) / std in double and rounds once.
 #include "gfx950_dialect.h"
 #include "../../include/mi355_unet3d.h"
+#define VOL_ZERO_WORDS                      // this source launches zero_words_kernel
+#include "volume_common.h"
 
-#define IN_MAX_VOXELS 2147483646ll          // voxel indices and counts stay in int32
 #define IN_WG 1024                          // most workgroups per channel of the streaming kernels = slots of partial sums
 #define PCT_PASSES 4                        // radix select: 4 passes of 8 bits over the key
 #define PCT_RANKS (2 * MI355_PERCENTILE_MAX_Q)
@@ -49,25 +48,6 @@ struct ZsScratch {                          // per channel
   int n, pad[3];
 };
 static_assert(sizeof(ZsScratch) == MI355_ZSCORE_SELECT_SCRATCH_BYTES, "MI355_ZSCORE_SELECT_SCRATCH_BYTES is the size of ZsScratch");
-
-static inline unsigned in_blocks(long long n, int per_block) { return (unsigned)((n + per_block - 1) / per_block); }
-
-static int in_check_dims(int32_t c, int64_t voxels) {
-  return (c < 1 || c > 65535 || voxels < 1 || voxels > IN_MAX_VOXELS) ? MI355_EINVAL : MI355_OK;
-}
-
-// a contiguous slice of `per` voxels (a multiple of 1024) per workgroup, at most IN_WG workgroups per channel
-static inline long long in_slice(long long V, int* nb) {
-  long long per = (V + IN_WG - 1) / IN_WG;
-  per = (per + 1023) / 1024 * 1024;
-  *nb = (int)((V + per - 1) / per);
-  return per;
-}
-
-__global__ void in_zero_kernel(int* p, long long n) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) p[i] = 0;
-}
 
 // four consecutive voxels of a channel: one 16-byte load where the address allows; `valid` = how many lie below `stop`
 __device__ __forceinline__ int in_load4(const float* x, long long i, long long stop, float v[4]) {
@@ -158,7 +138,7 @@ __global__ void __launch_bounds__(256) pct_hist_kernel(const float* x, const flo
     }
   }
   if (PASS == 0) {
-    for (int o = 32; o > 0; o >>= 1) nans += __shfl_xor(nans, o);
+    nans = wave_sum(nans);
     if (lane == 0) wnan[threadIdx.x >> 6] = nans;
   }
   __syncthreads();
@@ -170,12 +150,9 @@ __global__ void __launch_bounds__(256) pct_hist_kernel(const float* x, const flo
   }
 }
 
-// numpy's default ("linear") percentile: position p = q / 100 * (n - 1); the two ranks are floor(p) and floor(p) + 1 (clamped to n - 1)
-__device__ __forceinline__ double pct_position(double q, int n) { return q / 100.0 * (double)(n - 1); }
-
 struct PctQ { double q[MI355_PERCENTILE_MAX_Q]; };
 
-// thread r < ranks owns rank r = 2 * (index of q) + (0: lower, 1: upper)
+// thread r < ranks owns rank r = 2 * (index of q) + (0: lower, 1: upper) of numpy's linear rule (linear_rank)
 __global__ void pct_pick_kernel(int pass, PctQ qs, int ranks, PctScratch* scratch) {
   __shared__ unsigned chosen[PCT_RANKS];
   PctScratch* S = scratch + blockIdx.x;
@@ -199,22 +176,14 @@ __global__ void pct_pick_kernel(int pass, PctQ qs, int ranks, PctScratch* scratc
     unsigned prefix = 0u;
     int owner = 0;
     if (pass == 0) {
-      long long lo = (long long)floor(pct_position(qs.q[r >> 1], n));
-      lo = lo < 0 ? 0 : (lo > n - 1 ? n - 1 : lo);
-      k = (int)((r & 1) && lo + 1 <= n - 1 ? lo + 1 : lo);
+      k = linear_rank(qs.q[r >> 1], n, (r & 1) != 0);
     } else {
       k = S->rank[r];
       prefix = S->prefix[r];
       owner = S->leader[r];
     }
-    const int* hist = S->hist[pass][owner];
-    int below = 0, bin = 255;
-    for (int b = 0; b < 256; ++b) {
-      const int here = hist[b];
-      if (k < below + here) { bin = b; break; }
-      below += here;
-    }
-    next = (prefix << 8) | (unsigned)bin;
+    int below;
+    next = (prefix << 8) | (unsigned)radix_pick(S->hist[pass][owner], k, below);
     S->rank[r] = k - below;
   }
   if (threadIdx.x < PCT_RANKS) chosen[threadIdx.x] = next;
@@ -237,8 +206,8 @@ __global__ void pct_final_kernel(PctQ qs, int nq, const PctScratch* scratch, flo
   float lo = __uint_as_float(0x7fc00000u), hi = lo, val = lo;
   if (n > 0 && S->nan == 0) {
     lo = pct_value(S->prefix[2 * j]); hi = pct_value(S->prefix[2 * j + 1]);
-    const double p = pct_position(qs.q[j], n), frac = p - floor(p);
-    val = (float)(hi == lo ? (double)lo : (double)lo + frac * ((double)hi - (double)lo));      // (equal, infinite ones included: no inf - inf)
+    const double p = linear_position(qs.q[j], n);
+    val = (float)linear_blend((double)lo, (double)hi, p - floor(p));
   }
   out[(size_t)blockIdx.x * nq + j] = val;
   if (ranks_out) {
@@ -250,7 +219,7 @@ __global__ void pct_final_kernel(PctQ qs, int nq, const PctScratch* scratch, flo
 extern "C" int mi355_percentiles(const float* x, int32_t c, int64_t voxels, const double* q, int32_t nq, const float* above, float* out,
                                  float* ranks, int32_t* n, void* scratch, void* stream) {
   if (!x || !q || !out || !n || !scratch || (uintptr_t)scratch % 8 != 0) return MI355_EINVAL;
-  int rc = in_check_dims(c, voxels); if (rc) return rc;
+  int rc = vol_check_dims(c, voxels); if (rc) return rc;
   if (nq < 1 || nq > MI355_PERCENTILE_MAX_Q) return MI355_EINVAL;
   PctQ qs;
   for (int i = 0; i < MI355_PERCENTILE_MAX_Q; ++i) {
@@ -259,11 +228,11 @@ extern "C" int mi355_percentiles(const float* x, int32_t c, int64_t voxels, cons
   }
   const long long V = voxels;
   int nb;
-  const long long per = in_slice(V, &nb);
+  const long long per = vol_slice(V, 1024, IN_WG, &nb);
   const int nr = 2 * nq;
   PctScratch* S = (PctScratch*)scratch;
   const long long words = (long long)c * (long long)(sizeof(PctScratch) / 4);
-  LAUNCH(in_zero_kernel, dim3(in_blocks(words, 256)), dim3(256), 0, stream, (int*)scratch, words);
+  LAUNCH(zero_words_kernel, dim3(vol_blocks(words, 256)), dim3(256), 0, stream, (int*)scratch, words);
   rc = LAUNCH_CHECK(); if (rc) return rc;
   LAUNCH(pct_hist_kernel<0>, dim3(nb, c), dim3(256), 0, stream, x, above, V, per, nr, S);
   rc = LAUNCH_CHECK(); if (rc) return rc;
@@ -323,12 +292,12 @@ __global__ void __launch_bounds__(256) win_kernel(const float* x, int x_channels
 extern "C" int mi355_window(const float* x, int32_t x_channels, float* y, int32_t c, int64_t voxels, const float* lo, const float* hi,
                             int32_t mode, float floor_v, float ceiling, void* stream) {
   if (!x || !y || !lo) return MI355_EINVAL;
-  int rc = in_check_dims(c, voxels); if (rc) return rc;
+  int rc = vol_check_dims(c, voxels); if (rc) return rc;
   if (x_channels != c && x_channels != 1) return MI355_EINVAL;
   if (mode != MI355_WINDOW_CLAMP && mode != MI355_WINDOW_RESCALE && mode != MI355_WINDOW_SHIFT_FLOOR) return MI355_EINVAL;
   if (mode != MI355_WINDOW_SHIFT_FLOOR && !hi) return MI355_EINVAL;
   const long long V = voxels;
-  const dim3 grid(in_blocks(V, 1024), c);
+  const dim3 grid(vol_blocks(V, 1024), c);
   if (mode == MI355_WINDOW_CLAMP) LAUNCH(win_kernel<MI355_WINDOW_CLAMP>, grid, dim3(256), 0, stream, x, (int)x_channels, y, V, lo, hi, floor_v, ceiling);
   else if (mode == MI355_WINDOW_RESCALE) LAUNCH(win_kernel<MI355_WINDOW_RESCALE>, grid, dim3(256), 0, stream, x, (int)x_channels, y, V, lo, hi, floor_v, ceiling);
   else LAUNCH(win_kernel<MI355_WINDOW_SHIFT_FLOOR>, grid, dim3(256), 0, stream, x, (int)x_channels, y, V, lo, hi, floor_v, ceiling);
@@ -344,10 +313,6 @@ __device__ __forceinline__ bool zs_selected(float x, int select, float threshold
 __device__ __forceinline__ double zs_pivot(const float* xc) {
   const float p = xc[0];
   return (p - p == 0.f) ? (double)p : 0.0;                   // the channel's first voxel if it is finite
-}
-template <class T> __device__ __forceinline__ T in_wave_sum(T v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);   // a + b == b + a: every lane ends with the same bits
-  return v;
 }
 
 __global__ void __launch_bounds__(256) zs_partial_kernel(const float* x, long long V, long long per, int select, float threshold,
@@ -370,7 +335,7 @@ __global__ void __launch_bounds__(256) zs_partial_kernel(const float* x, long lo
       }
     }
   }
-  s = in_wave_sum(s); ss = in_wave_sum(ss); n = in_wave_sum(n);
+  s = wave_sum(s); ss = wave_sum(ss); n = wave_sum(n);
   if ((threadIdx.x & 63) == 0) { ws[0][threadIdx.x >> 6] = s; ws[1][threadIdx.x >> 6] = ss; wn[threadIdx.x >> 6] = n; }
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -422,19 +387,19 @@ __global__ void __launch_bounds__(256) zs_apply_kernel(const float* x, float* y,
 extern "C" int mi355_zscore_select(const float* x, float* y, int32_t c, int64_t voxels, int32_t select, float threshold, int32_t center,
                                    int32_t ddof, int32_t zero_std_to_one, int32_t* n, void* scratch, void* stream) {
   if (!x || !y || !n || !scratch || (uintptr_t)scratch % 8 != 0) return MI355_EINVAL;
-  int rc = in_check_dims(c, voxels); if (rc) return rc;
+  int rc = vol_check_dims(c, voxels); if (rc) return rc;
   if (select != MI355_SELECT_ALL && select != MI355_SELECT_NONZERO && select != MI355_SELECT_ABS_ABOVE) return MI355_EINVAL;
   if (ddof != 0 && ddof != 1) return MI355_EINVAL;
   if (select == MI355_SELECT_ABS_ABOVE && threshold != threshold) return MI355_EINVAL;
   const long long V = voxels;
   int nb;
-  const long long per = in_slice(V, &nb);
+  const long long per = vol_slice(V, 1024, IN_WG, &nb);
   ZsScratch* S = (ZsScratch*)scratch;
   LAUNCH(zs_partial_kernel, dim3(nb, c), dim3(256), 0, stream, x, V, per, (int)select, threshold, S);
   rc = LAUNCH_CHECK(); if (rc) return rc;
   LAUNCH(zs_final_kernel, dim3(c), dim3(64), 0, stream, x, V, nb, (int)(center != 0), (int)ddof, (int)(zero_std_to_one != 0), S, (int*)n);
   rc = LAUNCH_CHECK(); if (rc) return rc;
-  LAUNCH(zs_apply_kernel, dim3(in_blocks(V, 1024), c), dim3(256), 0, stream, x, y, V, (int)select, threshold, (const ZsScratch*)S);
+  LAUNCH(zs_apply_kernel, dim3(vol_blocks(V, 1024), c), dim3(256), 0, stream, x, y, V, (int)select, threshold, (const ZsScratch*)S);
   return LAUNCH_CHECK();
 }
 
@@ -459,7 +424,7 @@ __global__ void __launch_bounds__(256) thr_any_kernel(const float* x, int c, lon
 
 extern "C" int mi355_threshold_any(const float* x, int32_t c, int64_t voxels, const float* thr, uint8_t* out, void* stream) {
   if (!x || !thr || !out) return MI355_EINVAL;
-  int rc = in_check_dims(c, voxels); if (rc) return rc;
-  LAUNCH(thr_any_kernel, dim3(in_blocks(voxels, 1024)), dim3(256), 0, stream, x, (int)c, (long long)voxels, thr, (unsigned char*)out);
+  int rc = vol_check_dims(c, voxels); if (rc) return rc;
+  LAUNCH(thr_any_kernel, dim3(vol_blocks(voxels, 1024)), dim3(256), 0, stream, x, (int)c, (long long)voxels, thr, (unsigned char*)out);
   return LAUNCH_CHECK();
 }

@@ -1,12 +1,9 @@
 // Scoring a mask against the ground truth, on the device: overlap counts, mask edges, the exact Euclidean distance transform and the
 // surface-distance statistics (Hausdorff, percentile Hausdorff, average surface distance) that BraTS and SPPIN are ranked by.
 //
-// The rules of components.hip hold here too. NO WORKGROUP EVER WAITS FOR ANOTHER: no flag, no spin, no grid-wide barrier; whatever one
-// launch hands to the next crosses a kernel boundary. Every loop is bounded by an extent (a line length, a chunk, 256 bins, the fixed
-// number of partials). No allocation, copy or host wait inside the library. Workgroups meet only in INTEGER atomics (add on counters and
-// histogram bins, max on the bit pattern of a non-negative float): their result does not depend on arrival order, so two calls on the
-// same input give the same bits. Sums of distances are never accumulated atomically: every workgroup adds its own voxels in a fixed order
-// into a double, stores that partial in its own slot, and one thread adds the slots in index order.
+// The rules at the top of volume_common.h hold. The loops are bounded by a line length, a chunk, 256 bins or the fixed number of partials;
+// the integer atomics are adds on counters and histogram bins and max on the bit pattern of a non-negative float; the sums of distances
+// are per-workgroup doubles that one thread adds in index order.
 // Every op makes a fixed number of launches, whatever the data: seg_counts 2, mask_edges 1, edt 3, surface_stats 10.
 //
 //   seg_counts_kernel   4096 voxels per workgroup, 16 bytes per thread; three per-thread counts (pred, truth, both) reduced through the
@@ -29,8 +26,9 @@
 // most two roundings and each sum one: relative error < 5 * 2^-24.
 #include "gfx950_dialect.h"
 #include "../../include/mi355_unet3d.h"
+#define VOL_ZERO_WORDS                      // this source launches zero_words_kernel
+#include "volume_common.h"
 
-#define MT_MAX_VOXELS 2147483646ll          // the cap of mi355_cc_label: voxel indices and counts stay in int32
 #define CNT_PER_WG 4096                     // voxels per workgroup of seg_counts_kernel
 #define EDT_CHUNK 128                       // line elements per LDS stage of edt_line_kernel (x 64 columns x 4 bytes = 32 KiB)
 #define EDT_SEGS 4                          // 256 threads = 64 columns x 4 segments of the output chunk
@@ -49,19 +47,6 @@ struct SurfScratch {
   int pad[2];
 };
 static_assert(sizeof(SurfScratch) == MI355_SURFACE_SCRATCH_BYTES, "MI355_SURFACE_SCRATCH_BYTES is the size of SurfScratch");
-
-static inline unsigned mt_blocks(long long n, int per_block) { return (unsigned)((n + per_block - 1) / per_block); }
-
-static int mt_check_dims(int32_t c, int32_t d, int32_t h, int32_t w) {
-  if (c < 1 || c > 65535 || d < 1 || h < 1 || w < 1) return MI355_EINVAL;
-  if ((long long)d * h * w > MT_MAX_VOXELS) return MI355_EINVAL;
-  return MI355_OK;
-}
-
-__global__ void mt_zero_kernel(int* p, long long n) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) p[i] = 0;
-}
 
 // ---- a. overlap counts --------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void count_word(unsigned a, unsigned b, int& np, int& nt, int& tp) {
@@ -105,11 +90,11 @@ __global__ void __launch_bounds__(256) seg_counts_kernel(const unsigned char* pr
 extern "C" int mi355_seg_counts(const uint8_t* pred, const uint8_t* truth, int32_t c, int32_t d, int32_t h, int32_t w, int32_t* counts,
                                 void* stream) {
   if (!pred || !truth || !counts) return MI355_EINVAL;
-  int rc = mt_check_dims(c, d, h, w); if (rc) return rc;
+  int rc = vol_check_dims(c, d, h, w); if (rc) return rc;
   const long long V = (long long)d * h * w;
-  LAUNCH(mt_zero_kernel, dim3(mt_blocks(4ll * c, 256)), dim3(256), 0, stream, (int*)counts, 4ll * c);
+  LAUNCH(zero_words_kernel, dim3(vol_blocks(4ll * c, 256)), dim3(256), 0, stream, (int*)counts, 4ll * c);
   rc = LAUNCH_CHECK(); if (rc) return rc;
-  LAUNCH(seg_counts_kernel, dim3(mt_blocks(V, CNT_PER_WG), c), dim3(256), 0, stream, (const unsigned char*)pred, (const unsigned char*)truth,
+  LAUNCH(seg_counts_kernel, dim3(vol_blocks(V, CNT_PER_WG), c), dim3(256), 0, stream, (const unsigned char*)pred, (const unsigned char*)truth,
          V, (int*)counts);
   return LAUNCH_CHECK();
 }
@@ -133,8 +118,8 @@ __global__ void __launch_bounds__(256) mask_edges_kernel(const unsigned char* ma
 
 extern "C" int mi355_mask_edges(const uint8_t* mask, int32_t c, int32_t d, int32_t h, int32_t w, uint8_t* edges, void* stream) {
   if (!mask || !edges) return MI355_EINVAL;
-  int rc = mt_check_dims(c, d, h, w); if (rc) return rc;
-  LAUNCH(mask_edges_kernel, dim3(mt_blocks((long long)d * h * w, 256), c), dim3(256), 0, stream, (const unsigned char*)mask, (int)d, (int)h,
+  int rc = vol_check_dims(c, d, h, w); if (rc) return rc;
+  LAUNCH(mask_edges_kernel, dim3(vol_blocks((long long)d * h * w, 256), c), dim3(256), 0, stream, (const unsigned char*)mask, (int)d, (int)h,
          (int)w, (unsigned char*)edges);
   return LAUNCH_CHECK();
 }
@@ -220,11 +205,11 @@ static bool mt_bad_spacing(float s) { return !(s > 0.f) || !std::isfinite(s); }
 extern "C" int mi355_edt(const uint8_t* sites, int32_t invert, int32_t c, int32_t d, int32_t h, int32_t w, float sz, float sy, float sx,
                          float* dist2, float* tmp, void* stream) {
   if (!sites || !dist2 || !tmp || dist2 == tmp) return MI355_EINVAL;
-  int rc = mt_check_dims(c, d, h, w); if (rc) return rc;
+  int rc = vol_check_dims(c, d, h, w); if (rc) return rc;
   if (mt_bad_spacing(sz) || mt_bad_spacing(sy) || mt_bad_spacing(sx)) return MI355_EINVAL;
   const long long V = (long long)d * h * w, rows = (long long)d * h;
   const int tiles_x = ceil_div(w, 64);
-  LAUNCH(edt_x_kernel, dim3(mt_blocks(rows, 4), c), dim3(256), 0, stream, (const unsigned char*)sites, (int)(invert != 0), rows, (int)w, sx, dist2);
+  LAUNCH(edt_x_kernel, dim3(vol_blocks(rows, 4), c), dim3(256), 0, stream, (const unsigned char*)sites, (int)(invert != 0), rows, (int)w, sx, dist2);
   rc = LAUNCH_CHECK(); if (rc) return rc;
   LAUNCH(edt_line_kernel, dim3((unsigned)((long long)tiles_x * d), c), dim3(256), 0, stream, (const float*)dist2, tmp, (int)h, (long long)w,
          (long long)h * w, tiles_x, (int)w, V, sy);
@@ -241,11 +226,6 @@ extern "C" int mi355_edt(const uint8_t* sites, int32_t invert, int32_t c, int32_
 // prefix chosen so far (surf_stats_kernel is pass 0 for both ranks at once; surf_hist_kernel passes 1..3, a histogram per rank, since the
 // two ranks may have parted), and surf_pick_kernel walks the 256 bins to the one that holds the rank. No compaction, no sort.
 // A workgroup owns a contiguous slice of `per` voxels (a multiple of 256): thread t adds voxels t, t + 256, ... of the slice in order.
-template <class T> __device__ __forceinline__ T wave_sum(T v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);   // a + b == b + a: every lane ends with the same bits
-  return v;
-}
-
 __global__ void __launch_bounds__(256) surf_stats_kernel(const unsigned char* edges_a, const unsigned char* edges_b, const float* d2_ab,
                                                          const float* d2_ba, long long V, long long per, SurfScratch* scratch) {
   __shared__ int lh[2][256];
@@ -275,8 +255,7 @@ __global__ void __launch_bounds__(256) surf_stats_kernel(const unsigned char* ed
   for (int dir = 0; dir < 2; ++dir) {
     const double ws = wave_sum(s[dir]);
     const int wc = wave_sum(n[dir]);
-    unsigned wm = mx[dir];
-    for (int o = 32; o > 0; o >>= 1) { const unsigned om = __shfl_xor(wm, o); wm = om > wm ? om : wm; }
+    const unsigned wm = wave_max(mx[dir]);
     if ((threadIdx.x & 63) == 0) { wsum[dir][threadIdx.x >> 6] = ws; wn[dir][threadIdx.x >> 6] = wc; wmax[dir][threadIdx.x >> 6] = wm; }
   }
   __syncthreads();
@@ -316,9 +295,7 @@ __global__ void __launch_bounds__(256) surf_hist_kernel(const unsigned char* edg
     if (lh[k >> 1][k & 1][threadIdx.x] != 0) atomicAdd(&S->hist[pass][k >> 1][k & 1][threadIdx.x], lh[k >> 1][k & 1][threadIdx.x]);
 }
 
-// numpy's default ("linear") percentile: position p = q / 100 * (n - 1); the two ranks are floor(p) and floor(p) + 1 (clamped to n - 1)
-__device__ __forceinline__ double surf_position(double percentile, int n) { return percentile / 100.0 * (double)(n - 1); }
-
+// thread (dir, r) of a channel: rank r (0: lower, 1: upper; linear_rank) of direction dir, one byte further per pass
 __global__ void surf_pick_kernel(int pass, double percentile, SurfScratch* scratch) {
   SurfScratch* S = scratch + blockIdx.x;
   if (threadIdx.x >= 4) return;
@@ -328,20 +305,13 @@ __global__ void surf_pick_kernel(int pass, double percentile, SurfScratch* scrat
   int k;
   unsigned prefix = 0u;
   if (pass == 0) {
-    long long lo = (long long)floor(surf_position(percentile, n));
-    lo = lo < 0 ? 0 : (lo > n - 1 ? n - 1 : lo);
-    k = (int)(r && lo + 1 <= n - 1 ? lo + 1 : lo);
+    k = linear_rank(percentile, n, r != 0);
   } else {
     k = S->rank[dir][r];
     prefix = S->prefix[dir][r];
   }
-  const int* hist = S->hist[pass][dir][pass == 0 ? 0 : r];
-  int below = 0, bin = 255;
-  for (int b = 0; b < 256; ++b) {
-    const int here = hist[b];
-    if (k < below + here) { bin = b; break; }
-    below += here;
-  }
+  int below;
+  const int bin = radix_pick(S->hist[pass][dir][pass == 0 ? 0 : r], k, below);
   S->prefix[dir][r] = (prefix << 8) | (unsigned)bin;
   S->rank[dir][r] = k - below;
 }
@@ -369,8 +339,8 @@ __global__ void surf_final_kernel(int nb, double percentile, const SurfScratch* 
     const int n = dir ? nbv : na;
     hd[dir] = sqrtf(__uint_as_float((unsigned)S->maxbits[dir]));
     const double lo = (double)sqrtf(__uint_as_float(S->prefix[dir][0])), hi = (double)sqrtf(__uint_as_float(S->prefix[dir][1]));
-    const double p = surf_position(percentile, n), frac = p - floor(p);
-    pct[dir] = (float)(hi == lo ? lo : lo + frac * (hi - lo));                   // (equal, infinite ones included: no inf - inf)
+    const double p = linear_position(percentile, n);
+    pct[dir] = (float)linear_blend(lo, hi, p - floor(p));
   }
   o[0] = hd[0] > hd[1] ? hd[0] : hd[1];
   o[1] = pct[0] > pct[1] ? pct[0] : pct[1];
@@ -382,16 +352,14 @@ __global__ void surf_final_kernel(int nb, double percentile, const SurfScratch* 
 extern "C" int mi355_surface_stats(const uint8_t* edges_a, const uint8_t* edges_b, const float* dist2_ab, const float* dist2_ba, int32_t c,
                                    int64_t voxels, double percentile, float* out, int32_t* n, void* scratch, void* stream) {
   if (!edges_a || !edges_b || !dist2_ab || !dist2_ba || !out || !n || !scratch || (uintptr_t)scratch % 8 != 0) return MI355_EINVAL;
-  if (c < 1 || c > 65535 || voxels < 1 || voxels > MT_MAX_VOXELS) return MI355_EINVAL;
-  if (!(percentile >= 0.0 && percentile <= 100.0)) return MI355_EINVAL;
+  if (vol_check_dims(c, voxels) || !(percentile >= 0.0 && percentile <= 100.0)) return MI355_EINVAL;
   const long long V = voxels;
-  long long per = (V + SURF_WG - 1) / SURF_WG;
-  per = (per + 255) / 256 * 256;
-  const int nb = (int)((V + per - 1) / per);                // <= SURF_WG
+  int nb;                                                   // <= SURF_WG
+  const long long per = vol_slice(V, 256, SURF_WG, &nb);
   SurfScratch* S = (SurfScratch*)scratch;
   const unsigned char *ea = (const unsigned char*)edges_a, *eb = (const unsigned char*)edges_b;
   const long long words = (long long)c * (long long)(sizeof(SurfScratch) / 4);
-  LAUNCH(mt_zero_kernel, dim3(mt_blocks(words, 256)), dim3(256), 0, stream, (int*)scratch, words);
+  LAUNCH(zero_words_kernel, dim3(vol_blocks(words, 256)), dim3(256), 0, stream, (int*)scratch, words);
   int rc = LAUNCH_CHECK(); if (rc) return rc;
   LAUNCH(surf_stats_kernel, dim3(nb, c), dim3(256), 0, stream, ea, eb, dist2_ab, dist2_ba, V, per, S);
   rc = LAUNCH_CHECK(); if (rc) return rc;

@@ -8,6 +8,7 @@
 //        (datasets/segmentation.py:77-86): per-channel (x - mean) / std, population std, std == 0 -> 1.
 #include "gfx950_dialect.h"
 #include "../../include/mi355_unet3d.h"
+#include "volume_common.h"
 
 #define PP_MAX_C 16
 
@@ -82,7 +83,7 @@ extern "C" int mi355_one_hot(const float* label_map, int64_t voxels, const float
   return LAUNCH_CHECK();
 }
 
-// z-score: per-channel shifted sums (K = first voxel) -> mean, 1/std -> apply
+// z-score: per-channel shifted sums (K = first voxel) -> mean, 1/std (shifted_mean_rstd) -> apply
 #define ZS_BLOCKS 256
 __global__ void zscore_partial_kernel(const float* x, long long V, float* ws) {
   __shared__ float r0[256], r1[256];
@@ -93,12 +94,7 @@ __global__ void zscore_partial_kernel(const float* x, long long V, float* ws) {
   for (long long v = (long long)blk * blockDim.x + threadIdx.x; v < V; v += (long long)gridDim.x * blockDim.x) {
     const float t = xc[v] - K; s0 += t; s1 += t * t;
   }
-  r0[threadIdx.x] = s0; r1[threadIdx.x] = s1;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) { r0[threadIdx.x] += r0[threadIdx.x + s]; r1[threadIdx.x] += r1[threadIdx.x + s]; }
-    __syncthreads();
-  }
+  block_sum_256(r0, r1, s0, s1);
   if (threadIdx.x == 0) { ws[((size_t)c * gridDim.x + blk) * 2] = r0[0]; ws[((size_t)c * gridDim.x + blk) * 2 + 1] = r1[0]; }
 }
 __global__ void zscore_finalize_kernel(const float* x, long long V, int B, float* ws, float* stats) {
@@ -106,13 +102,7 @@ __global__ void zscore_finalize_kernel(const float* x, long long V, int B, float
   if (threadIdx.x != 0) return;
   double s0 = 0.0, s1 = 0.0;
   for (int b = 0; b < B; ++b) { s0 += (double)ws[((size_t)c * B + b) * 2]; s1 += (double)ws[((size_t)c * B + b) * 2 + 1]; }
-  const double K = (double)x[(size_t)c * V];
-  const double mean = K + s0 / (double)V;
-  double var = (s1 - s0 * s0 / (double)V) / (double)V;       // population variance (torch.std(unbiased=False))
-  if (var < 0.0) var = 0.0;
-  double sd = sqrt(var);
-  if (sd == 0.0) sd = 1.0;                                    // MONAI NormalizeIntensity: divisor 0 -> 1
-  stats[2 * c] = (float)mean; stats[2 * c + 1] = (float)(1.0 / sd);
+  shifted_mean_rstd((double)x[(size_t)c * V], s0, s1, (double)V, stats[2 * c], stats[2 * c + 1]);
 }
 __global__ void zscore_apply_kernel(const float* x, float* y, long long V, int C, const float* stats) {
   const long long total = (long long)C * V;
@@ -148,44 +138,14 @@ __global__ void resample_affine_kernel(const float* src, float* dst, int C, int 
     float cy = M.m[4] * z + M.m[5] * y + M.m[6] * x + M.m[7];
     float cx = M.m[8] * z + M.m[9] * y + M.m[10] * x + M.m[11];
     if (mode != MI355_RESAMPLE_TRILINEAR) {
-      const float rz = mode == MI355_RESAMPLE_NEAREST ? rintf(cz) : floorf(cz);
-      const float ry = mode == MI355_RESAMPLE_NEAREST ? rintf(cy) : floorf(cy);
-      const float rx = mode == MI355_RESAMPLE_NEAREST ? rintf(cx) : floorf(cx);
-      int iz = (int)rz, iy = (int)ry, ix = (int)rx;
-      const bool inside = iz >= 0 && iy >= 0 && ix >= 0 && iz < sd && iy < sh && ix < sw;
-      iz = iz < 0 ? 0 : (iz < sd ? iz : sd - 1); iy = iy < 0 ? 0 : (iy < sh ? iy : sh - 1); ix = ix < 0 ? 0 : (ix < sw ? ix : sw - 1);
-      const size_t o = ((size_t)iz * sh + iy) * sw + ix;
+      bool inside;
+      const size_t o = nearest_source(cz, cy, cx, mode != MI355_RESAMPLE_NEAREST, sd, sh, sw, inside);
       for (int c = 0; c < C; ++c) dst[(size_t)c * DV + v] = (padding == 1 && !inside) ? 0.f : src[(size_t)c * SV + o];
       continue;
     }
-    if (padding == 0) {
-      cz = cz < 0.f ? 0.f : (cz > (float)(sd - 1) ? (float)(sd - 1) : cz);
-      cy = cy < 0.f ? 0.f : (cy > (float)(sh - 1) ? (float)(sh - 1) : cy);
-      cx = cx < 0.f ? 0.f : (cx > (float)(sw - 1) ? (float)(sw - 1) : cx);
-    }
-    const float fz = floorf(cz), fy = floorf(cy), fx = floorf(cx);
-    const float lz = cz - fz, ly = cy - fy, lx = cx - fx;
-    const int z0 = (int)fz, y0 = (int)fy, x0 = (int)fx;
     float wgt[8]; size_t off[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const int a = k >> 2, b = (k >> 1) & 1, e = k & 1;
-      int iz = z0 + a, iy = y0 + b, ix = x0 + e;
-      float w = (a ? lz : 1.f - lz) * (b ? ly : 1.f - ly) * (e ? lx : 1.f - lx);
-      const bool inside = iz >= 0 && iy >= 0 && ix >= 0 && iz < sd && iy < sh && ix < sw;
-      if (!inside) {
-        if (padding == 1) w = 0.f;               // zeros outside; with border padding the clamp above leaves only weight-0 corners outside
-        iz = iz < 0 ? 0 : (iz < sd ? iz : sd - 1); iy = iy < 0 ? 0 : (iy < sh ? iy : sh - 1); ix = ix < 0 ? 0 : (ix < sw ? ix : sw - 1);
-      }
-      wgt[k] = w; off[k] = ((size_t)iz * sh + iy) * sw + ix;
-    }
-    for (int c = 0; c < C; ++c) {
-      const float* sc = src + (size_t)c * SV;
-      // x pairs first, then y, then z
-      const float v00 = wgt[0] * sc[off[0]] + wgt[1] * sc[off[1]], v01 = wgt[2] * sc[off[2]] + wgt[3] * sc[off[3]];
-      const float v10 = wgt[4] * sc[off[4]] + wgt[5] * sc[off[5]], v11 = wgt[6] * sc[off[6]] + wgt[7] * sc[off[7]];
-      dst[(size_t)c * DV + v] = (v00 + v01) + (v10 + v11);
-    }
+    trilinear_setup(cz, cy, cx, sd, sh, sw, padding, wgt, off);
+    for (int c = 0; c < C; ++c) dst[(size_t)c * DV + v] = trilinear_blend(src + (size_t)c * SV, wgt, off);
   }
 }
 

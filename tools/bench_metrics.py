@@ -32,7 +32,7 @@ C, DHW = 3, (240, 240, 155)
 NOTES = {"seg_counts_kernel": "read 2", "mask_edges_kernel": "read 1 (+ 6 neighbours from cache), write 1",
          "edt_x_kernel": "read 1 twice, write 4, read 4, write 4", "edt_line_kernel": "read 4 x ceil(L / 128) chunks, write 4",
          "surf_stats_kernel": "read 2 (+ 4 at edge voxels)", "surf_hist_kernel": "read 2 (+ 4 at edge voxels)",
-         "surf_pick_kernel": "256 bins", "surf_final_kernel": "partials in index order", "mt_zero_kernel": "clears counters / scratch"}
+         "surf_pick_kernel": "256 bins", "surf_final_kernel": "partials in index order", "zero_words_kernel": "clears counters / scratch"}
 
 
 def make_pair(seed=0):
