@@ -120,7 +120,9 @@ def build(force=False, verbose=True):
     with ThreadPoolExecutor(max_workers=8) as ex:
         list(ex.map(run, jobs))
     if jobs or not os.path.exists(OUT):
-        run([cc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", OUT] + objs)
+        # --no-undefined: a cross-file declaration that drifted from its definition (csrc/conv_internal.h) fails the build here, not the
+        # import of the package with an unresolved mangled name
+        run([cc, "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,--no-undefined", "-o", OUT] + objs)
     return OUT
 
 

@@ -23,6 +23,7 @@
 #include "conv3d_lp.h"
 #include "pack_values.h"
 #include "act_io.h"
+#include "conv_internal.h"
 #ifndef LP_GNB_BATCH
 #define LP_GNB_BATCH 4
 #endif
@@ -505,7 +506,7 @@ __global__ void pack_weight_bf16_kernel(const float* w, unsigned short* wp, int 
 extern "C" size_t mi355_packed_weight_bytes_bf16(int32_t cout, int32_t cin, int32_t kd, int32_t precision) {
   const int ns = lp_nsplit(precision);
   if (!ns) return 0;
-  const int coutP = (cout + 31) / 32 * 32, cinP = (cin + 15) / 16 * 16;
+  const int coutP = pad32(cout), cinP = pad16(cin);
   return (size_t)kd * kd * kd * cinP * coutP * ns * 2;
 }
 
@@ -513,10 +514,9 @@ extern "C" int mi355_pack_conv_weight_bf16(const float* w, void* wp, int32_t cou
                                            int32_t precision, void* stream) {
   const int ns = lp_nsplit(precision);
   if (!w || !wp || cout <= 0 || cin <= 0 || kd != 3 || mode < 0 || mode > 1 || !ns) return MI355_EINVAL;
-  const int coutP = (cout + 31) / 32 * 32, cinP = (cin + 15) / 16 * 16;
+  const int coutP = pad32(cout), cinP = pad16(cin);
   const size_t total = (size_t)27 * cinP * coutP;
-  int grid = (int)((total + 255) / 256); if (grid > 4096) grid = 4096;
-  LAUNCH(pack_weight_bf16_kernel, dim3(grid), dim3(256), 0, stream, w, (unsigned short*)wp, cout, cin, 27, coutP, cinP, mode, ns,
+  LAUNCH(pack_weight_bf16_kernel, dim3(pack_grid(total)), dim3(256), 0, stream, w, (unsigned short*)wp, cout, cin, 27, coutP, cinP, mode, ns,
          precision == MI355_PREC_F16 ? 1 : 0);
   return LAUNCH_CHECK();
 }
@@ -532,7 +532,7 @@ static int launch_b(ConvBArgs& a, int in_mode, void* stream) {
   a.coTiles = ceil_div(a.Cout, 32 * WN * NT);
   a.spatialTiles = a.N * a.tilesZ * a.tilesY * a.tilesX;
   const long long blocks = (long long)a.spatialTiles * a.coTiles;
-  if (blocks <= 0 || blocks > 0x7fffffffLL) return MI355_EINVAL;
+  if (!grid_fits(blocks)) return MI355_EINVAL;
   if (a.g.mom && a.g.gnb) return MI355_EUNSUPPORTED;
   if (a.g.mom) {
     if (in_mode == MI355_IN_PLAIN)
@@ -616,7 +616,7 @@ static LpPlan plan_lp(const mi355_act* x, const mi355_act* y, const mi355_conv_d
   // plane-ring kernels: one record per (z range, column); zring2 leaves one per wave and half-wave of the column's workgroup (x 8)
   else if (p.zp.use) b = (long long)p.zp.zsplits * p.zp.tilesY * p.zp.tilesX * (p.zp.use == 2 ? 8 : 1);
   else b = (long long)ceil_div(Do, p.tile.big ? 4 : 2) * ceil_div(Ho, 4) * ceil_div(Wo, 16);
-  p.stats_blocks = b > 0 && b <= 0x7fffffffLL ? (int32_t)b : 0;
+  p.stats_blocks = records_or_0(b);
   return p;
 }
 
@@ -640,8 +640,6 @@ int mi355_conv3d_bf16_kernel_name(const mi355_act* x, const mi355_act* y, const 
   return 0;
 }
 
-int mi355_fill_gn_fuse(GnFuseArgs& g, const mi355_act* x, const mi355_act* y, const mi355_conv_desc* d);      // conv3d_fwd.hip
-
 // called by mi355_conv3d_fwd (conv3d_fwd.hip) when desc->precision selects a bf16 path and the problem qualifies
 int mi355_conv3d_fwd_bf16_impl(const mi355_act* x, const void* wp, const mi355_act* y, const mi355_conv_desc* d, void* stream) {
   const LpPlan p = plan_lp(x, y, d);
@@ -659,8 +657,8 @@ int mi355_conv3d_fwd_bf16_impl(const mi355_act* x, const void* wp, const mi355_a
   a.res = (const float*)d->residual; a.resld = d->residual_ld;
   a.in_scale = d->in_scale; a.in_shift = d->in_shift; a.slope = d->act_slope; a.in_slope = d->in_slope;
   a.out_chscale = d->out_chscale; a.bias = d->bias;
-  a.N = x->n; a.Di = x->d; a.Hi = x->h; a.Wi = x->w; a.Cin = x->c; a.CinP = (x->c + 15) / 16 * 16;
-  a.Do = d->out_d; a.Ho = d->out_h; a.Wo = d->out_w; a.Cout = y->c; a.CoutP = (y->c + 31) / 32 * 32;
+  a.N = x->n; a.Di = x->d; a.Hi = x->h; a.Wi = x->w; a.Cin = x->c; a.CinP = pad16(x->c);
+  a.Do = d->out_d; a.Ho = d->out_h; a.Wo = d->out_w; a.Cout = y->c; a.CoutP = pad32(y->c);
   a.yD = y->d; a.yH = y->h; a.yW = y->w; a.offz = d->off_z; a.offy = d->off_y; a.offx = d->off_x;
   a.pad = d->pad;
   if (a.res && a.resld < a.Cout) return MI355_EINVAL;
@@ -670,7 +668,7 @@ int mi355_conv3d_fwd_bf16_impl(const mi355_act* x, const void* wp, const mi355_a
     if (a.g.gnb && d->in_mode != MI355_IN_PLAIN) return MI355_EUNSUPPORTED;
     a.tilesY = zp.tilesY; a.tilesX = zp.tilesX; a.zsplits = zp.zsplits; a.zper = zp.zper;
     const long long blocks = (long long)a.N * zp.zsplits * zp.tilesY * zp.tilesX;
-    if (blocks <= 0 || blocks > 0x7fffffffLL) return MI355_EINVAL;
+    if (!grid_fits(blocks)) return MI355_EINVAL;
     const int fuse = a.g.mom ? 1 : (a.g.gnb ? 2 : 0);
     const bool f16 = d->precision == MI355_PREC_F16;
     if (zp.use == 2) {

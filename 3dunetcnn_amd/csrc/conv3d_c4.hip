@@ -15,6 +15,7 @@
 #include "../../include/mi355_unet3d.h"
 #include "gn_fuse.h"
 #include "act_io.h"
+#include "conv_internal.h"
 
 struct C4Args {
   const float* x; int xld;
@@ -583,7 +584,7 @@ int mi355_conv3d_c4_fwd_impl(const mi355_act* x, const float* w, const mi355_act
   a.mom = d->moments_out;
   a.tilesZ = ceil_div(a.D, 4); a.tilesY = ceil_div(a.H, 8); a.tilesX = ceil_div(a.W, 8); a.coTiles = ceil_div(a.Cout, 32);
   const long long blocks = (long long)a.N * a.tilesZ * a.tilesY * a.tilesX * a.coTiles;
-  if (blocks <= 0 || blocks > 0x7fffffffLL) return MI355_EINVAL;
+  if (!grid_fits(blocks)) return MI355_EINVAL;
   if (d->precision != MI355_PREC_F32) {
     // bf16 matrix pipe with split operands: a workgroup walks a.ntiles z tiles of its (y, x) column; enough z chunks for >= ~2048 workgroups
     const long long cols = (long long)a.N * a.tilesY * a.tilesX * a.coTiles;
@@ -621,7 +622,7 @@ int mi355_conv3d_c4_fwd_impl(const mi355_act* x, const float* w, const mi355_act
 static int c4_wgrad_plan(const mi355_act* x, const mi355_act* dy, C4Args& a) {
   a.tilesZ = ceil_div(x->d, 4); a.tilesY = ceil_div(x->h, 4); a.tilesX = ceil_div(x->w, 8); a.coTiles = ceil_div(dy->c, 32);
   const long long nt = (long long)x->n * a.tilesZ * a.tilesY * a.tilesX;
-  if (nt <= 0 || nt > 0x7fffffffLL) return 0;
+  if (!grid_fits(nt)) return 0;
   a.ntiles = (int)nt;
   int splits = ceil_div(1024, a.coTiles);
   const int max_splits = a.ntiles >= 8 ? a.ntiles / 8 : 1;
@@ -669,7 +670,7 @@ int mi355_conv3d_narrow_impl(const mi355_act* x, const float* wp, const mi355_ac
   a.N = x->n; a.D = x->d; a.H = x->h; a.W = x->w; a.Cq = x->c / 4; a.CinQ = (x->c + 7) / 8 * 2; a.Cout = y->c;
   a.tilesZ = ceil_div(a.D, 4); a.tilesY = ceil_div(a.H, 8); a.tilesX = ceil_div(a.W, 8);
   const long long sp = (long long)a.N * a.tilesZ * a.tilesY * a.tilesX;
-  if (sp <= 0 || sp > 0x7fffffffLL) return MI355_EINVAL;
+  if (!grid_fits(sp)) return MI355_EINVAL;
   a.spatialTiles = (int)sp;
   // 16 input channels per LDS chunk: 38.4 KB and 103 VGPRs -> four workgroups per CU (measured on the 128^3 batch-2 layer: 0.53 ms;
   // 32-channel chunks, two workgroups per CU: 0.67 ms; 8-channel chunks: 0.96 ms)

@@ -23,6 +23,7 @@
 #include "gfx950_dialect.h"
 #include "../../include/mi355_unet3d.h"
 #include "act_io.h"
+#include "conv_internal.h"
 
 // v_mfma_f32_4x4x1_16b_f32: 16 independent 4 x 4 outer products. Lane l = 4 b + r supplies A[b][row r] and B[b][column r]; it holds
 // D[b][rows 0..3][column r] in its 4 result registers.
@@ -51,8 +52,6 @@ struct C4BArgs {
   const float* mean_rstd; int groups;
   int N, D, H, W, tilesY, tilesX, zchunks, zper;
 };
-
-void conv3d_c4_wgrad_reduce_launch(const float* ws, float* dw, int Cout, int splits, void* stream);      // conv3d_c4.hip
 
 // TD: storage type of dy (act_io.h). The arithmetic is exact fp32 on the stored values in every precision mode, as in the kernels this one
 // replaces (the 4-channel first layer's weight gradient and data gradient never ran on the 16-bit pipe).
@@ -284,7 +283,7 @@ __global__ __launch_bounds__(512) MIN_WAVES_PER_SIMD(2) void conv3d_c4_bwd(C4BAr
 static int c4b_plan(const mi355_act* x, C4BArgs& a) {
   a.tilesY = ceil_div(x->h, 8); a.tilesX = ceil_div(x->w, 16);
   const long long cols = (long long)x->n * a.tilesY * a.tilesX;
-  if (cols <= 0 || cols > 0x7fffffffLL) return 0;
+  if (!grid_fits(cols)) return 0;
   // enough z chunks for ~512 workgroups (one per CU, two rounds), at least 8 planes each (a chunk re-reads two halo planes)
   int zch = (int)((512 + cols - 1) / cols);
   const int maxch = x->d >= 8 ? x->d / 8 : 1;
@@ -302,7 +301,7 @@ static int c4b_ok(const mi355_act* x, const mi355_act* dy, const mi355_conv_desc
   if (x->dtype != MI355_ACT_F32 || !act_dtype_ok(dy)) return MI355_EUNSUPPORTED;      // (any precision mode: this layer's backward is exact fp32 in all of them)
   if (x->n != dy->n || x->d != dy->d || x->h != dy->h || x->w != dy->w) return MI355_EINVAL;
   if (x->ld % 4 || dy->ld % 4 || x->ld < 4 || dy->ld < 32 || ((uintptr_t)x->p & 15) || ((uintptr_t)dy->p & act_align_mask(dy->dtype))) return MI355_EINVAL;
-  if (d->in_mode == MI355_IN_AFFINE_ACT && (!d->in_scale || !d->in_shift || !(d->act_slope >= 0.f && d->act_slope <= 1.f))) return MI355_EINVAL;
+  if (!affine_prologue_ok(d)) return MI355_EINVAL;
   return MI355_OK;
 }
 

@@ -17,6 +17,7 @@
 #include "gn_fuse.h"
 #include "pack_values.h"
 #include "act_io.h"
+#include "conv_internal.h"
 
 struct ConvArgs {
   const float* x; int xld;
@@ -668,18 +669,17 @@ extern "C" int mi355_pack_weights_batch(const mi355_pack_task* tasks, int32_t nt
 
 extern "C" size_t mi355_packed_weight_elems(int32_t cout, int32_t cin, int32_t kd, int32_t mode) {
   (void)mode;
-  const int coutP = (cout + 31) / 32 * 32, cinP = (cin + 7) / 8 * 8;
+  const int coutP = pad32(cout), cinP = pad8(cin);
   return (size_t)kd * kd * kd * cinP * coutP;
 }
 
 // cout/cin are the PACKED roles (for dgrad packs pass cout := original cin, cin := original cout).
 extern "C" int mi355_pack_conv_weight(const float* w, float* wp, int32_t cout, int32_t cin, int32_t kd, int32_t mode, void* stream) {
   if (!w || !wp || cout <= 0 || cin <= 0 || (kd != 1 && kd != 3) || mode < 0 || mode > 3) return MI355_EINVAL;
-  const int coutP = (cout + 31) / 32 * 32, cinP = (cin + 7) / 8 * 8;
+  const int coutP = pad32(cout), cinP = pad8(cin);
   const int T = kd * kd * kd;
   const size_t total = (size_t)T * cinP * coutP;
-  int grid = (int)((total + 255) / 256); if (grid > 4096) grid = 4096;
-  LAUNCH(pack_weight_kernel, dim3(grid), dim3(256), 0, stream, w, wp, cout, cin, T, coutP, cinP, mode);
+  LAUNCH(pack_weight_kernel, dim3(pack_grid(total)), dim3(256), 0, stream, w, wp, cout, cin, T, coutP, cinP, mode);
   return LAUNCH_CHECK();
 }
 
@@ -714,23 +714,6 @@ static bool stats_fusable(const mi355_act* x, const mi355_act* y, const mi355_co
   if ((d->kd != 1 && d->kd != 3) || (d->stride != 1 && d->stride != 2)) return false;
   return true;
 }
-
-int mi355_conv3d_fwd_bf16_impl(const mi355_act* x, const void* wp, const mi355_act* y, const mi355_conv_desc* d, void* stream);
-int mi355_conv3d_bf16_kernel_name(const mi355_act* x, const mi355_act* y, const mi355_conv_desc* d, char* out, size_t n);
-int32_t mi355_conv3d_bf16_stats_blocks(const mi355_act* x, const mi355_act* y, const mi355_conv_desc* d);
-int mi355_conv3d_c4_ok(const mi355_act* x, const mi355_conv_desc* d);
-int mi355_conv3d_c4_fwd_impl(const mi355_act* x, const float* w, const mi355_act* y, const mi355_conv_desc* d, void* stream);
-int mi355_conv3d_narrow_ok(const mi355_act* x, const mi355_act* y, const mi355_conv_desc* d);
-int mi355_conv3d_narrow_impl(const mi355_act* x, const float* wp, const mi355_act* y, const mi355_conv_desc* d, void* stream);
-// conv3d_s2.hip: the z-marching 32 -> 32 channel stride-2 forward
-int mi355_conv3d_s2c32_ok(const mi355_act* x, const mi355_act* y, const mi355_conv_desc* d);
-int32_t mi355_conv3d_s2c32_stats_blocks(const mi355_act* y);
-int mi355_conv3d_s2c32_fwd_impl(const mi355_act* x, const float* wp, const mi355_act* y, const mi355_conv_desc* d, void* stream);
-int mi355_conv3d_s2c32_dgrad_ok(const mi355_act* x, const mi355_act* y, const mi355_conv_desc* d);
-// conv3d_k1_stream.hip: 1x1x1 forward / data gradient of bf16 tensors as wave streams
-int mi355_conv3d_k1_stream_ok(const mi355_act* x, const mi355_act* y, const mi355_conv_desc* d);
-int mi355_conv3d_k1_stream_impl(const mi355_act* x, const float* wp, const mi355_act* y, const mi355_conv_desc* d, void* stream);
-int mi355_conv3d_s2c32_dgrad_impl(const mi355_act* x, const float* wp, const mi355_act* y, const mi355_conv_desc* d, void* stream);
 
 extern "C" int mi355_conv3d_uses_bf16(const mi355_conv_desc* d) {
   return d && d->precision != MI355_PREC_F32 && d->kd == 3 && d->stride == 1 &&
@@ -778,14 +761,14 @@ static FwdPlan plan_fwd(const mi355_act* x, const mi355_act* y, const mi355_conv
     // two-level accumulation: always for >= 4 channel chunks; for the 1-tile-per-wave configurations (16 accumulator
     // registers, deep layers) already from 2 chunks, where it is free
     // (not for the 4-tile configuration: 64 more live registers would cost a wave of occupancy per SIMD)
-    const int cinP = (x->c + 7) / 8 * 8, cinL = d->in_mode == MI355_IN_S2D ? 8 * x->c : x->c;
+    const int cinP = pad8(x->c), cinL = d->in_mode == MI355_IN_S2D ? 8 * x->c : x->c;
     p.tl = d->kd == 3 && c.tiles <= 2 && (cinP >= 4 * c.kc || (c.tiles == 1 && cinP >= 2 * c.kc));
-    p.fullj = (cinL + 7) / 8 * 8 % c.kc == 0;
+    p.fullj = pad8(cinL) % c.kc == 0;
     // only the 3x3x3 kernels reading a plain / normalised input carry the fused-statistics epilogue
     if (fusable && d->kd == 3 && (d->in_mode == MI355_IN_PLAIN || d->in_mode == MI355_IN_AFFINE_ACT))
       b = (long long)ceil_div(y->d, c.tz) * ceil_div(y->h, c.ty) * ceil_div(y->w, c.tx);
   }
-  if (b > 0 && b <= 0x7fffffffLL) p.stats_blocks = (int32_t)b;
+  if (grid_fits(b)) p.stats_blocks = (int32_t)b;
   return p;
 }
 
@@ -805,7 +788,7 @@ static int launch_cfg(ConvArgs& a, int in_mode, const FwdPlan& p, void* stream) 
   a.tilesZ = ceil_div(a.Do, TZ); a.tilesY = ceil_div(a.Ho, TY); a.tilesX = ceil_div(a.Wo, TX);
   a.coTiles = ceil_div(a.Cout, 32 * WN * NT);
   const long long blocks = (long long)a.N * a.tilesZ * a.tilesY * a.tilesX * a.coTiles;
-  if (blocks <= 0 || blocks > 0x7fffffffLL) return MI355_EINVAL;
+  if (!grid_fits(blocks)) return MI355_EINVAL;
   const bool tl = p.tl, fullj = p.fullj;
   const int fuse = p.fuse;
   if (fuse && (KD != 3 || (in_mode != MI355_IN_PLAIN && in_mode != MI355_IN_AFFINE_ACT))) return MI355_EUNSUPPORTED;
@@ -871,7 +854,7 @@ extern "C" int32_t mi355_conv3d_stats_blocks(const mi355_act* x, const mi355_act
   return plan_fwd(x, y, d).stats_blocks;
 }
 
-// (also the 16-bit forward's, conv3d_bf16.hip)
+// the one validation and copy of a statistics request (also the 16-bit forward's, conv3d_bf16.hip, and the Winograd kernels', wino_common.h)
 int mi355_fill_gn_fuse(GnFuseArgs& g, const mi355_act* x, const mi355_act* y, const mi355_conv_desc* d) {
   memset(&g, 0, sizeof(g));
   if (!d->moments_out && !d->gn_bwd) return 0;
@@ -893,8 +876,7 @@ extern "C" int mi355_conv3d_fwd(const mi355_act* x, const float* wp, const mi355
   if ((d->kd != 1 && d->kd != 3) || (d->stride != 1 && d->stride != 2)) return MI355_EUNSUPPORTED;
   if (x->c % 4 || x->ld % 4 || x->ld < x->c || y->ld < y->c || x->n != y->n || !act_dtype_ok(x) || !act_dtype_ok(y)) return MI355_EINVAL;
   if (((uintptr_t)x->p & act_align_mask(x->dtype)) || ((uintptr_t)wp & 15)) return MI355_EINVAL;
-  if (d->in_mode == MI355_IN_AFFINE_ACT && (!d->in_scale || !d->in_shift)) return MI355_EINVAL;
-  if (d->in_mode == MI355_IN_AFFINE_ACT && !(d->act_slope >= 0.f && d->act_slope <= 1.f)) return MI355_EINVAL;   // act(u) = max(u, slope*u)
+  if (!affine_prologue_ok(d)) return MI355_EINVAL;
   if (d->in_mode < 0 || d->in_mode > 3) return MI355_EINVAL;
   if ((d->in_mode == MI355_IN_S2D || d->out_mode == MI355_OUT_D2S) && d->kd != 1) return MI355_EUNSUPPORTED;
   if (d->in_mode == MI355_IN_S2D && d->out_mode == MI355_OUT_D2S) return MI355_EUNSUPPORTED;
@@ -919,8 +901,8 @@ extern "C" int mi355_conv3d_fwd(const mi355_act* x, const float* wp, const mi355
   a.res = (const float*)d->residual; a.resld = d->residual_ld;
   a.in_scale = d->in_scale; a.in_shift = d->in_shift; a.slope = d->act_slope;
   a.out_chscale = d->out_chscale; a.bias = d->bias;
-  a.N = x->n; a.Di = x->d; a.Hi = x->h; a.Wi = x->w; a.Cin = x->c; a.CinP = (x->c + 7) / 8 * 8;
-  a.Do = d->out_d; a.Ho = d->out_h; a.Wo = d->out_w; a.Cout = y->c; a.CoutP = (y->c + 31) / 32 * 32;
+  a.N = x->n; a.Di = x->d; a.Hi = x->h; a.Wi = x->w; a.Cin = x->c; a.CinP = pad8(x->c);
+  a.Do = d->out_d; a.Ho = d->out_h; a.Wo = d->out_w; a.Cout = y->c; a.CoutP = pad32(y->c);
   a.yD = y->d; a.yH = y->h; a.yW = y->w; a.offz = d->off_z; a.offy = d->off_y; a.offx = d->off_x;
   a.pad = d->pad;
   a.in_slope = d->in_slope; a.outmode = d->out_mode; a.cD = a.cH = a.cW = 1; a.fC = 4;
@@ -937,7 +919,7 @@ extern "C" int mi355_conv3d_fwd(const mi355_act* x, const float* wp, const mi355
     if (im == MI355_IN_S2D) {
       // x is the fine tensor: the conv runs on the coarse grid (= y's grid) with 8*x->c logical input channels
       if (x->d != 2 * y->d || x->h != 2 * y->h || x->w != 2 * y->w || a.residual_or_chscale()) return MI355_EINVAL;
-      f.cD = y->d; f.cH = y->h; f.cW = y->w; f.fC = x->c; f.Cin = 8 * x->c; f.CinP = (f.Cin + 7) / 8 * 8;
+      f.cD = y->d; f.cH = y->h; f.cW = y->w; f.fC = x->c; f.Cin = 8 * x->c; f.CinP = pad8(f.Cin);
       vin = vout;
     } else if (d->out_mode == MI355_OUT_D2S) {
       // y is the fine tensor: the conv runs on x's grid with 8*y->c logical output channels

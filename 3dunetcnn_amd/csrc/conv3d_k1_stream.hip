@@ -20,6 +20,7 @@
 #include <cstdlib>
 #include "../../include/mi355_unet3d.h"
 #include "act_io.h"
+#include "conv_internal.h"
 
 struct K1SArgs {
   const bf16_t* x; int xld;
@@ -172,7 +173,7 @@ int mi355_conv3d_k1_stream_impl(const mi355_act* x, const float* wp, const mi355
   const K1SPlan p = plan_k1s(x, y, d);
   if (!p.ok) return MI355_EUNSUPPORTED;
   K1SArgs a; memset(&a, 0, sizeof(a));
-  a.x = (const bf16_t*)x->p; a.xld = x->ld; a.wp = wp; a.coutP = (y->c + 31) / 32 * 32;
+  a.x = (const bf16_t*)x->p; a.xld = x->ld; a.wp = wp; a.coutP = pad32(y->c);
   a.y = (bf16_t*)y->p; a.yld = y->ld; a.res = (const bf16_t*)d->residual; a.resld = d->residual_ld;
   a.V = p.V; a.nchunks = p.nchunks; a.chunksPer = p.chunksPer;
   if (p.cik == 2) LAUNCH((conv3d_k1_stream_bf16<2, 2>), dim3((unsigned)p.grid), dim3(256), 0, stream, a);

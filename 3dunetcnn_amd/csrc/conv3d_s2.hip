@@ -16,6 +16,7 @@
 #include "gfx950_dialect.h"
 #include "../../include/mi355_unet3d.h"
 #include "act_io.h"
+#include "conv_internal.h"
 
 struct S2Args {
   const float* x; int xld;
@@ -498,7 +499,7 @@ __global__ __launch_bounds__(256) MIN_WAVES_PER_SIMD(2) void conv3d_s2c32_dgrad(
 static int s2_plan(const mi355_act* y, S2Args& a, int target = 256) {
   a.tilesY = ceil_div(y->h, 4); a.tilesX = ceil_div(y->w, 8);
   const long long cols1 = (long long)a.tilesY * a.tilesX, cols = cols1 * y->n;
-  if (cols <= 0 || cols > 0x7fffffffLL) return 0;
+  if (!grid_fits(cols)) return 0;
   // z chunks PER SAMPLE (~256 workgroups per sample in the forward: two per CU and one round at batch 2; 1024 in all measured 0.332 -> below):
   // the moments records of a sample -- and with them the bits of its normalised output -- must not depend on how many samples ride along
   // (tests/test_fullsize_gpu.py: a sample alone equals the same sample in a batch, bit for bit)
@@ -574,8 +575,6 @@ int mi355_conv3d_s2c32_dgrad_impl(const mi355_act* x, const float* wp, const mi3
             LAUNCH((conv3d_s2c32_dgrad<TA>), dim3((unsigned)wgs), dim3(256), lds_bytes, stream, a));
   return LAUNCH_CHECK();
 }
-
-int mi355_wgrad_reduce_launch(const float* ws, float* dw, int Cout, int Cin, int T, int SL, int ciTiles, void* stream);      // conv3d_wgrad.hip
 
 // the weight gradient of the same calls (x: input of the conv, dy: gradient of its output; plain input): MI355_S2_KERNEL=0 -> never
 int mi355_conv3d_s2c32_wgrad_ok(const mi355_act* x, const mi355_act* dy, const mi355_conv_desc* d) {

@@ -18,6 +18,7 @@
 #include "gfx950_dialect.h"
 #include "../../include/mi355_unet3d.h"
 #include "act_io.h"
+#include "conv_internal.h"
 
 struct WgradArgs {
   const float* x; int xld;
@@ -435,28 +436,6 @@ int mi355_wgrad_reduce_launch(const float* ws, float* dw, int Cout, int Cin, int
   return LAUNCH_CHECK();
 }
 
-size_t mi355_conv3d_wgrad_bf16_workspace(const mi355_act* x, const mi355_act* dy, const mi355_conv_desc* d);
-int mi355_conv3d_wgrad_bf16_impl(const mi355_act* x, const mi355_act* dy, float* dw, const mi355_conv_desc* d,
-                                 void* ws, size_t ws_bytes, void* stream);
-int mi355_conv3d_c4_ok(const mi355_act* x, const mi355_conv_desc* d);
-size_t mi355_conv3d_c4_wgrad_workspace(const mi355_act* x, const mi355_act* dy, const mi355_conv_desc* d);
-int mi355_conv3d_c4_wgrad_impl(const mi355_act* x, const mi355_act* dy, float* dw, const mi355_conv_desc* d,
-                               void* ws, size_t ws_bytes, void* stream);
-// conv3d_s2.hip: the z-marching 32 -> 32 channel stride-2 weight gradient
-int mi355_conv3d_s2c32_wgrad_ok(const mi355_act* x, const mi355_act* dy, const mi355_conv_desc* d);
-size_t mi355_conv3d_s2c32_wgrad_workspace(const mi355_act* dy);
-int mi355_conv3d_s2c32_wgrad_impl(const mi355_act* x, const mi355_act* dy, float* dw, const mi355_conv_desc* d, void* ws, size_t ws_bytes,
-                                  void* stream);
-// conv3d_wgrad_lp.hip: the z-marching 3x3x3 weight gradient of 16-bit tensors (LDS transpose reads)
-int mi355_conv3d_wgrad_lp_tr_ok(const mi355_act* x, const mi355_act* dy, const mi355_conv_desc* d);
-size_t mi355_conv3d_wgrad_lp_tr_workspace(const mi355_act* x, const mi355_act* dy, const mi355_conv_desc* d);
-int mi355_conv3d_wgrad_lp_tr_impl(const mi355_act* x, const mi355_act* dy, float* dw, const mi355_conv_desc* d, void* ws, size_t ws_bytes,
-                                  void* stream);
-int mi355_conv3d_wgrad_k1_lp_ok(const mi355_act* x, const mi355_act* dy, const mi355_conv_desc* d);
-size_t mi355_conv3d_wgrad_k1_lp_workspace(const mi355_act* x, const mi355_act* dy, const mi355_conv_desc* d);
-int mi355_conv3d_wgrad_k1_lp_impl(const mi355_act* x, const mi355_act* dy, float* dw, const mi355_conv_desc* d, void* ws, size_t ws_bytes,
-                                  void* stream);
-
 struct WgradPlan { int tz, ty, tx, ntiles, tilesZ, tilesY, tilesX, splits, ciTiles, coTiles, wv, coutL; size_t ws_bytes; int ok; };
 
 static WgradPlan plan_wgrad(const mi355_act* x, const mi355_act* dy, const mi355_conv_desc* d) {
@@ -476,7 +455,7 @@ static WgradPlan plan_wgrad(const mi355_act* x, const mi355_act* dy, const mi355
   p.tilesZ = ceil_div(Do, p.tz); p.tilesY = ceil_div(Ho, p.ty); p.tilesX = ceil_div(Wo, p.tx);
   const long long nt = (long long)dy->n * p.tilesZ * p.tilesY * p.tilesX;
   p.coutL = coutL;
-  if (nt <= 0 || nt > 0x7fffffffLL) return p;
+  if (!grid_fits(nt)) return p;
   p.ntiles = (int)nt;
   p.ciTiles = ceil_div(x->c, 32); p.coTiles = ceil_div(coutL, 32);
   const int pairs = p.ciTiles * p.coTiles;
@@ -580,8 +559,7 @@ extern "C" int mi355_conv3d_wgrad(const mi355_act* x, const mi355_act* dy, float
   if (x->c % 4 || x->ld % 4 || dy->c % 4 || dy->ld % 4 || x->n != dy->n || !act_dtype_ok(x) || !act_dtype_ok(dy)) return MI355_EINVAL;
   if (((uintptr_t)x->p & act_align_mask(x->dtype)) || ((uintptr_t)dy->p & act_align_mask(dy->dtype))) return MI355_EINVAL;
   if (d->in_mode != MI355_IN_PLAIN && d->in_mode != MI355_IN_AFFINE_ACT) return MI355_EUNSUPPORTED;
-  if (d->in_mode == MI355_IN_AFFINE_ACT && (!d->in_scale || !d->in_shift)) return MI355_EINVAL;
-  if (d->in_mode == MI355_IN_AFFINE_ACT && !(d->act_slope >= 0.f && d->act_slope <= 1.f)) return MI355_EINVAL;
+  if (!affine_prologue_ok(d)) return MI355_EINVAL;
   if (d->precision < MI355_PREC_F32 || d->precision > MI355_PREC_F16) return MI355_EINVAL;
   const WgradRoute route = route_wgrad(x, dy, d);
   switch (route) {

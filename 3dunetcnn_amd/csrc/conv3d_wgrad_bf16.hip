@@ -20,8 +20,7 @@
 #include <cstdlib>
 #include "../../include/mi355_unet3d.h"
 #include "act_io.h"
-
-int mi355_wgrad_reduce_launch(const float* ws, float* dw, int Cout, int Cin, int T, int SL, int ciTiles, void* stream);
+#include "conv_internal.h"
 
 struct WgradBArgs {
   const float* x; int xld;
@@ -447,7 +446,7 @@ static WBPlan plan_wb(const mi355_act* x, const mi355_act* dy, const mi355_conv_
   if (x->d != dy->d || x->h != dy->h || x->w != dy->w) return p;
   p.tilesY = ceil_div(dy->h, 4); p.tilesX = ceil_div(dy->w, 16);
   const long long nt = (long long)dy->n * p.tilesY * p.tilesX * dy->d;
-  if (nt <= 0 || nt > 0x7fffffffLL) return p;
+  if (!grid_fits(nt)) return p;
   p.ntiles = (int)nt;
   p.ciTiles = ceil_div(x->c, 32); p.coTiles32 = ceil_div(dy->c, 32);
   p.mt = (dy->c > 32 && lp_nsplit(d->precision) < 3) ? 2 : 1;     // 3 planes x 64 co would not fit the 160 KiB LDS

@@ -29,8 +29,7 @@
 #include <cstdlib>
 #include "../../include/mi355_unet3d.h"
 #include "act_io.h"
-
-int mi355_wgrad_reduce_launch(const float* ws, float* dw, int Cout, int Cin, int T, int SL, int ciTiles, void* stream);
+#include "conv_internal.h"
 
 // ds_read_b64_tr_b16 and its CPU twin for the emulated build (tools/emu: fibers, one per lane; the 16 row addresses travel by shuffle)
 #ifdef MI355_EMU

@@ -24,8 +24,7 @@
 #include "gfx950_dialect.h"
 #include <type_traits>
 #include "../../include/mi355_unet3d.h"
-
-int mi355_wgrad_reduce_launch(const float* ws, float* dw, int Cout, int Cin, int T, int SL, int ciTiles, void* stream);
+#include "conv_internal.h"
 
 struct WWRArgs {
   const float* x; int xld;
@@ -288,7 +287,7 @@ static WWRPlan plan_wwr(const mi355_act* x, const mi355_act* dy, const mi355_con
   if (x->c % 4 || x->ld % 4 || dy->c % 4 || dy->ld % 4 || ((uintptr_t)x->p & 15) || ((uintptr_t)dy->p & 15)) return p;
   p.tilesY = ceil_div(dy->h, 4); p.tilesX = ceil_div(dy->w, 8);
   const long long nc = (long long)dy->n * p.tilesY * p.tilesX;
-  if (nc <= 0 || nc > 0x7fffffffLL) return p;
+  if (!grid_fits(nc)) return p;
   p.ncols = (int)nc;
   p.ciTiles = ceil_div(x->c, 32); p.coTiles = ceil_div(dy->c, 32);
   const int pairs = p.ciTiles * p.coTiles;
@@ -315,7 +314,7 @@ extern "C" int mi355_conv3d_wgrad_wino(const mi355_act* x, const mi355_act* dy, 
   const WWRPlan p = plan_wwr(x, dy, d);
   if (!p.ok) return MI355_EUNSUPPORTED;
   if (ws_bytes < p.ws_bytes) return MI355_EWORKSPACE;
-  if (d->in_mode == MI355_IN_AFFINE_ACT && (!d->in_scale || !d->in_shift || !(d->act_slope >= 0.f && d->act_slope <= 1.f))) return MI355_EINVAL;
+  if (!affine_prologue_ok(d)) return MI355_EINVAL;
   WWRArgs a;
   a.x = (const float*)x->p; a.xld = x->ld; a.dy = (const float*)dy->p; a.dyld = dy->ld; a.ws = (float*)ws;
   a.in_scale = d->in_scale; a.in_shift = d->in_shift; a.slope = d->act_slope; a.in_slope = d->in_slope;

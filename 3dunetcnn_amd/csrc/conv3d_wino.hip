@@ -30,6 +30,7 @@
 #include "gn_fuse.h"
 #include "pack_values.h"
 #include "wino_common.h"
+#include "conv_internal.h"
 
 #ifndef WINO_ZBRICK
 #define WINO_ZBRICK 8             // z tiles per brick of the workgroup order (A/B: -DWINO_ZBRICK=1 = x fastest)
@@ -521,16 +522,15 @@ __global__ void wino_pack_weight_kernel(const float* w, float* up, int cout, int
 
 extern "C" size_t mi355_wino_weight_elems(int32_t cout, int32_t cin) {
   if (cout <= 0 || cin <= 0) return 0;
-  const size_t coutP = (cout + 31) / 32 * 32, cinP = (cin + 7) / 8 * 8;
+  const size_t coutP = pad32(cout), cinP = pad8(cin);
   return (size_t)48 * cinP * coutP;
 }
 
 extern "C" int mi355_wino_pack_weight(const float* w, float* up, int32_t cout, int32_t cin, int32_t mode, void* stream) {
   if (!w || !up || cout <= 0 || cin <= 0 || mode < 0 || mode > 1) return MI355_EINVAL;
-  const int coutP = (cout + 31) / 32 * 32, cinP = (cin + 7) / 8 * 8;     // logical packed dims: cout = "out", cin = "in" of THIS conv
+  const int coutP = pad32(cout), cinP = pad8(cin);     // logical packed dims: cout = "out", cin = "in" of THIS conv
   const size_t items = (size_t)3 * cinP * coutP;
-  int grid = (int)((items + 255) / 256); if (grid > 4096) grid = 4096;
-  LAUNCH(wino_pack_weight_kernel, dim3(grid), dim3(256), 0, stream, w, up, cout, cin, coutP, cinP, mode);
+  LAUNCH(wino_pack_weight_kernel, dim3(pack_grid(items)), dim3(256), 0, stream, w, up, cout, cin, coutP, cinP, mode);
   return LAUNCH_CHECK();
 }
 
@@ -542,39 +542,12 @@ extern "C" int mi355_conv3d_wino_fwd(const mi355_act* x, const float* up, const 
   if (!up || ((uintptr_t)up & 15)) return MI355_EINVAL;
   { const int rc = wino_check(x, y, d); if (rc) return rc; }
   WinoArgs a;
-  memset(&a.g, 0, sizeof(a.g));
-  a.g.mom = d->moments_out;
-  if (d->gn_bwd) {
-    const mi355_gn_bwd_fuse* f = d->gn_bwd;
-    if (!f->gx || !f->scale || !f->shift || !f->mean_rstd || !f->partials_out || f->groups <= 0 || y->c % f->groups || f->gx_ld < y->c) return MI355_EINVAL;
-    a.g.gnb = f->partials_out; a.g.gx = (const float*)f->gx; a.g.gxld = f->gx_ld; a.g.gscale = f->scale; a.g.gshift = f->shift; a.g.gmr = f->mean_rstd;
-    a.g.ggroups = f->groups; a.g.gslope = f->act_slope;
-  }
-  a.x = (const float*)x->p; a.xld = x->ld; a.up = up; a.y = (float*)y->p; a.yld = y->ld;
-  a.res = (const float*)d->residual; a.resld = d->residual_ld;
-  a.in_scale = d->in_scale; a.in_shift = d->in_shift; a.slope = d->act_slope; a.in_slope = d->in_slope;
-  a.out_chscale = d->out_chscale; a.bias = d->bias;
-  a.N = x->n; a.D = x->d; a.H = x->h; a.W = x->w; a.Cin = x->c; a.CinP = (x->c + 7) / 8 * 8;
-  a.Cout = y->c; a.CoutP = (y->c + 31) / 32 * 32;
-  a.tilesZ = ceil_div(a.D, 2); a.tilesY = ceil_div(a.H, 8); a.tilesX = ceil_div(a.W, 16); a.coTiles = a.CoutP / 32;
-  a.vec4 = a.Cout % 4 == 0 && a.yld % 4 == 0 && !((uintptr_t)a.y & 15) && (!a.res || (a.resld % 4 == 0 && !((uintptr_t)a.res & 15))) &&
-           (!a.g.gnb || (a.g.gxld % 4 == 0 && !((uintptr_t)a.g.gx & 15)));
-  const long long blocks = (long long)a.N * a.tilesZ * a.tilesY * a.tilesX * a.coTiles;
-  if (blocks <= 0 || blocks > 0x7fffffffLL) return MI355_EINVAL;
-  const dim3 grid((unsigned)blocks), blk(512);
+  long long blocks;
+  { const int rc = wino_fill_args(a, blocks, x, up, y, d, pad8(x->c)); if (rc) return rc; }
   // 4 staged plane chunks + 3 weight slabs (75 264 bytes; the padded exchange of the epilogue, 73 728, lives inside) + norm prologue: two
   // workgroups per CU
   const int lds_bytes = (4 * 1632 + 3 * 4096 + 3 * a.CinP) * (int)sizeof(float);
-#define WINO_LAUNCH(IM, FU)                                                                          \
-  do { SET_MAX_DYN_LDS((conv3d_wino2d_d8<IM, FU>), lds_bytes);                                         \
-       LAUNCH((conv3d_wino2d_d8<IM, FU>), grid, blk, lds_bytes, stream, a); } while (0)
-  if (a.g.mom) {
-    if (d->in_mode == MI355_IN_PLAIN) WINO_LAUNCH(MI355_IN_PLAIN, 1); else WINO_LAUNCH(MI355_IN_AFFINE_ACT, 1);
-  } else if (a.g.gnb) {
-    WINO_LAUNCH(MI355_IN_PLAIN, 2);
-  } else if (d->in_mode == MI355_IN_PLAIN) WINO_LAUNCH(MI355_IN_PLAIN, 0);
-  else WINO_LAUNCH(MI355_IN_AFFINE_ACT, 0);
-#undef WINO_LAUNCH
+  WINO_LAUNCH(conv3d_wino2d_d8, 512, lds_bytes);
   return LAUNCH_CHECK();
 }
 
@@ -582,5 +555,5 @@ extern "C" int mi355_conv3d_wino_fwd(const mi355_act* x, const float* up, const 
 extern "C" int32_t mi355_conv3d_wino_stats_blocks(const mi355_act* y) {
   if (!y) return 0;
   const long long b = (long long)ceil_div(y->d, 2) * ceil_div(y->h, 8) * ceil_div(y->w, 16);
-  return b > 0 && b <= 0x7fffffffLL ? (int32_t)b : 0;
+  return records_or_0(b);
 }

@@ -41,6 +41,7 @@
 #include "gn_fuse.h"
 #include "pack_values.h"
 #include "wino_common.h"
+#include "conv_internal.h"
 
 #ifndef WINO3_ZBRICK
 #define WINO3_ZBRICK 8            // z tiles per brick of the workgroup order
@@ -468,16 +469,15 @@ __global__ void wino3_pack_weight_kernel(const float* w, float* up, int cout, in
 // cout / cin: the PACKED roles (out / in channels of THIS conv). cin is padded to the channel quad, cout to the 32-channel tile.
 extern "C" size_t mi355_wino3d_weight_elems(int32_t cout, int32_t cin) {
   if (cout <= 0 || cin <= 0) return 0;
-  const size_t coutP = (cout + 31) / 32 * 32, cinP = (cin + 3) / 4 * 4;
+  const size_t coutP = pad32(cout), cinP = (cin + 3) / 4 * 4;
   return (size_t)64 * cinP * coutP;
 }
 
 extern "C" int mi355_wino3d_pack_weight(const float* w, float* up, int32_t cout, int32_t cin, int32_t mode, void* stream) {
   if (!w || !up || cout <= 0 || cin <= 0 || mode < 0 || mode > 1) return MI355_EINVAL;
-  const int coutP = (cout + 31) / 32 * 32, cinP = (cin + 3) / 4 * 4;
+  const int coutP = pad32(cout), cinP = (cin + 3) / 4 * 4;
   const size_t items = (size_t)cinP * coutP;
-  int grid = (int)((items + 255) / 256); if (grid > 4096) grid = 4096;
-  LAUNCH(wino3_pack_weight_kernel, dim3(grid), dim3(256), 0, stream, w, up, cout, cin, coutP, cinP, mode);
+  LAUNCH(wino3_pack_weight_kernel, dim3(pack_grid(items)), dim3(256), 0, stream, w, up, cout, cin, coutP, cinP, mode);
   return LAUNCH_CHECK();
 }
 
@@ -499,38 +499,11 @@ extern "C" int mi355_conv3d_wino3d_fwd(const mi355_act* x, const float* up, cons
   if (!up || ((uintptr_t)up & 15)) return MI355_EINVAL;
   { const int rc = wino3_check(x, y, d); if (rc) return rc; }
   WinoArgs a;
-  memset(&a.g, 0, sizeof(a.g));
-  a.g.mom = d->moments_out;
-  if (d->gn_bwd) {
-    const mi355_gn_bwd_fuse* f = d->gn_bwd;
-    if (!f->gx || !f->scale || !f->shift || !f->mean_rstd || !f->partials_out || f->groups <= 0 || y->c % f->groups || f->gx_ld < y->c) return MI355_EINVAL;
-    a.g.gnb = f->partials_out; a.g.gx = (const float*)f->gx; a.g.gxld = f->gx_ld; a.g.gscale = f->scale; a.g.gshift = f->shift; a.g.gmr = f->mean_rstd;
-    a.g.ggroups = f->groups; a.g.gslope = f->act_slope;
-  }
-  a.x = (const float*)x->p; a.xld = x->ld; a.up = up; a.y = (float*)y->p; a.yld = y->ld;
-  a.res = (const float*)d->residual; a.resld = d->residual_ld;
-  a.in_scale = d->in_scale; a.in_shift = d->in_shift; a.slope = d->act_slope; a.in_slope = d->in_slope;
-  a.out_chscale = d->out_chscale; a.bias = d->bias;
-  a.N = x->n; a.D = x->d; a.H = x->h; a.W = x->w; a.Cin = x->c; a.CinP = x->c;
-  a.Cout = y->c; a.CoutP = (y->c + 31) / 32 * 32;
-  a.tilesZ = ceil_div(a.D, 2); a.tilesY = ceil_div(a.H, 8); a.tilesX = ceil_div(a.W, 16); a.coTiles = a.CoutP / 32;
-  a.vec4 = a.Cout % 4 == 0 && a.yld % 4 == 0 && !((uintptr_t)a.y & 15) && (!a.res || (a.resld % 4 == 0 && !((uintptr_t)a.res & 15))) &&
-           (!a.g.gnb || (a.g.gxld % 4 == 0 && !((uintptr_t)a.g.gx & 15)));
-  const long long blocks = (long long)a.N * a.tilesZ * a.tilesY * a.tilesX * a.coTiles;
-  if (blocks <= 0 || blocks > 0x7fffffffLL) return MI355_EINVAL;
-  const dim3 grid((unsigned)blocks), blk(1024);
+  long long blocks;
+  { const int rc = wino_fill_args(a, blocks, x, up, y, d, x->c); if (rc) return rc; }
   // 4 staged chunks (52 224 bytes) + 3 weight slabs (98 304) + norm prologue; the exchange of the epilogue (147 456) lives inside: one
   // workgroup per CU
   const int lds_bytes = (4 * 3264 + 3 * 8192 + 3 * a.Cin) * (int)sizeof(float);
-#define WINO3_LAUNCH(IM, FU)                                                                         \
-  do { SET_MAX_DYN_LDS((conv3d_wino3d<IM, FU>), lds_bytes);                                            \
-       LAUNCH((conv3d_wino3d<IM, FU>), grid, blk, lds_bytes, stream, a); } while (0)
-  if (a.g.mom) {
-    if (d->in_mode == MI355_IN_PLAIN) WINO3_LAUNCH(MI355_IN_PLAIN, 1); else WINO3_LAUNCH(MI355_IN_AFFINE_ACT, 1);
-  } else if (a.g.gnb) {
-    WINO3_LAUNCH(MI355_IN_PLAIN, 2);
-  } else if (d->in_mode == MI355_IN_PLAIN) WINO3_LAUNCH(MI355_IN_PLAIN, 0);
-  else WINO3_LAUNCH(MI355_IN_AFFINE_ACT, 0);
-#undef WINO3_LAUNCH
+  WINO_LAUNCH(conv3d_wino3d, 1024, lds_bytes);
   return LAUNCH_CHECK();
 }

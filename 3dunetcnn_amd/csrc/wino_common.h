@@ -1,10 +1,11 @@
 // Shared by the two Winograd forward / dgrad kernels of the 3x3x3 stride-1 convolution: conv3d_wino.hip (F(2x2, 3x3) in the plane x direct z)
-// and conv3d_wino3d.hip (F(2x2x2, 3x3x3)). Argument block, the statistics tail of the fused epilogues, the eligibility check.
+// and conv3d_wino3d.hip (F(2x2x2, 3x3x3)). Argument block, statistics tail of the fused epilogues, eligibility check, the entry points' host path.
 #pragma once
 #include "gfx950_dialect.h"
 #include <cstdlib>
 #include "../../include/mi355_unet3d.h"
 #include "gn_fuse.h"
+#include "conv_internal.h"
 
 struct WinoArgs {
   const float* x; int xld;
@@ -119,10 +120,42 @@ static inline int wino_check(const mi355_act* x, const mi355_act* y, const mi355
   if (d->off_z || d->off_y || d->off_x || d->out_d != y->d || d->out_h != y->h || d->out_w != y->w) return MI355_EUNSUPPORTED;
   if (x->d != y->d || x->h != y->h || x->w != y->w || x->n != y->n) return MI355_EINVAL;
   if (x->c % 4 || x->ld % 4 || x->ld < x->c || y->ld < y->c || ((uintptr_t)x->p & 15)) return MI355_EINVAL;
-  if (d->in_mode == MI355_IN_AFFINE_ACT && (!d->in_scale || !d->in_shift || !(d->act_slope >= 0.f && d->act_slope <= 1.f))) return MI355_EINVAL;
+  if (!affine_prologue_ok(d)) return MI355_EINVAL;
   if (d->residual && d->residual_ld < y->c) return MI355_EINVAL;
   if (d->moments_out && d->gn_bwd) return MI355_EUNSUPPORTED;
   if (d->gn_bwd && d->in_mode != MI355_IN_PLAIN) return MI355_EUNSUPPORTED;
   return MI355_OK;
 }
 
+// The arguments of a call wino_check accepted, and its workgroup count: one per (sample, 2 x 8 x 16 tile, 32 output channels). CinP: the
+// input channels as the kernel's weight pack pads them. Returns the status of a statistics request mi355_fill_gn_fuse refuses, or
+// MI355_EINVAL for a grid that does not fit.
+static inline int wino_fill_args(WinoArgs& a, long long& blocks, const mi355_act* x, const float* up, const mi355_act* y, const mi355_conv_desc* d,
+                                 int CinP) {
+  { const int rc = mi355_fill_gn_fuse(a.g, x, y, d); if (rc) return rc; }
+  a.x = (const float*)x->p; a.xld = x->ld; a.up = up; a.y = (float*)y->p; a.yld = y->ld;
+  a.res = (const float*)d->residual; a.resld = d->residual_ld;
+  a.in_scale = d->in_scale; a.in_shift = d->in_shift; a.slope = d->act_slope; a.in_slope = d->in_slope;
+  a.out_chscale = d->out_chscale; a.bias = d->bias;
+  a.N = x->n; a.D = x->d; a.H = x->h; a.W = x->w; a.Cin = x->c; a.CinP = CinP;
+  a.Cout = y->c; a.CoutP = pad32(y->c);
+  a.tilesZ = ceil_div(a.D, 2); a.tilesY = ceil_div(a.H, 8); a.tilesX = ceil_div(a.W, 16); a.coTiles = a.CoutP / 32;
+  a.vec4 = a.Cout % 4 == 0 && a.yld % 4 == 0 && !((uintptr_t)a.y & 15) && (!a.res || (a.resld % 4 == 0 && !((uintptr_t)a.res & 15))) &&
+           (!a.g.gnb || (a.g.gxld % 4 == 0 && !((uintptr_t)a.g.gx & 15)));
+  blocks = (long long)a.N * a.tilesZ * a.tilesY * a.tilesX * a.coTiles;
+  return grid_fits(blocks) ? MI355_OK : MI355_EINVAL;
+}
+
+// Launches KERNEL<in_mode, fuse> on the filled arguments `a` of descriptor `d`: fuse 1 with a moments request, 2 with the norm-backward sums
+// (plain input only: wino_check), else 0. BLOCK: threads per workgroup; LDSB: dynamic LDS bytes.
+#define WINO_LAUNCH_FORM(KERNEL, BLOCK, LDSB, IM, FU)                                                  \
+  do { SET_MAX_DYN_LDS((KERNEL<IM, FU>), (LDSB));                                                      \
+       LAUNCH((KERNEL<IM, FU>), dim3((unsigned)blocks), dim3(BLOCK), (LDSB), stream, a); } while (0)
+#define WINO_LAUNCH(KERNEL, BLOCK, LDSB)                                                                        \
+  do {                                                                                                          \
+    if (a.g.mom && d->in_mode == MI355_IN_PLAIN) WINO_LAUNCH_FORM(KERNEL, BLOCK, LDSB, MI355_IN_PLAIN, 1);      \
+    else if (a.g.mom) WINO_LAUNCH_FORM(KERNEL, BLOCK, LDSB, MI355_IN_AFFINE_ACT, 1);                            \
+    else if (a.g.gnb) WINO_LAUNCH_FORM(KERNEL, BLOCK, LDSB, MI355_IN_PLAIN, 2);                                 \
+    else if (d->in_mode == MI355_IN_PLAIN) WINO_LAUNCH_FORM(KERNEL, BLOCK, LDSB, MI355_IN_PLAIN, 0);            \
+    else WINO_LAUNCH_FORM(KERNEL, BLOCK, LDSB, MI355_IN_AFFINE_ACT, 0);                                         \
+  } while (0)

@@ -3,8 +3,9 @@ that select the large-volume routes cost nothing). Run as a child process by tes
 
     MI355_EMU_NOEXEC=1 python tests/route_cases.py   -> one JSON object {case id: result}
 
-For every case: the kernel the config query names, the kernels the launch recorded (tools/emu: emu_take_launches), the launch's status, and
-what the workspace / statistics-block query answered together with the status of a launch that relies on that answer."""
+For every case: the kernel the config query names, the kernels the launch recorded (tools/emu: emu_take_launches) with their grid, block
+and dynamic LDS bytes (emu_take_geometry), the launch's status, and what the workspace / statistics-block query answered together with
+the status of a launch that relies on that answer."""
 import ctypes
 import importlib
 import json
@@ -61,11 +62,13 @@ def _backend():
     lib_mod = importlib.import_module("3dunetcnn_amd._lib")
     ops = importlib.import_module("3dunetcnn_amd.ops")
     cdll = ctypes.CDLL(so)
-    cdll.emu_take_launches.restype, cdll.emu_take_launches.argtypes = ctypes.c_size_t, [ctypes.c_char_p, ctypes.c_size_t]
+    for take in (cdll.emu_take_launches, cdll.emu_take_geometry):
+        take.restype, take.argtypes = ctypes.c_size_t, [ctypes.c_char_p, ctypes.c_size_t]
     return ops, ops.Backend(lib=lib_mod.bind(cdll), device="cpu")
 
 
-def main():
+def collect():
+    """{case id: result} of every case of FWD and WGRAD."""
     import torch
     assert os.environ.get("MI355_EMU_NOEXEC") == "1", "route cases only record launches: run with MI355_EMU_NOEXEC=1"
     ops, be = _backend()
@@ -74,6 +77,10 @@ def main():
 
     def take():
         lib.emu_take_launches(buf, len(buf))
+        return [k for k in buf.value.decode().split("\n") if k]
+
+    def geometry():
+        lib.emu_take_geometry(buf, len(buf))
         return [k for k in buf.value.decode().split("\n") if k]
 
     def act(spec):
@@ -100,9 +107,9 @@ def main():
             xd, yd = x.desc(), y.desc()
             r = {"config_rc": lib.mi355_conv3d_fwd_config(ctypes.byref(xd), ctypes.byref(yd), ctypes.byref(d), buf, 96)}
             r["config"] = buf.value.decode()
-            take()
+            take(), geometry()
             r["rc"] = lib.mi355_conv3d_fwd(ctypes.byref(xd), w.data_ptr(), ctypes.byref(yd), ctypes.byref(d), None)
-            r["launched"] = take()
+            r["launched"], r["geometry"] = take(), geometry()
             # the statistics query, and a launch with the moments epilogue it allows or refuses
             r["stats_blocks"] = lib.mi355_conv3d_stats_blocks(ctypes.byref(xd), ctypes.byref(yd), ctypes.byref(d))
             rec = torch.zeros(max(r["stats_blocks"], 1) * ys[0] * ys[4] * 3)
@@ -110,7 +117,7 @@ def main():
             r["config_moments_rc"] = lib.mi355_conv3d_fwd_config(ctypes.byref(xd), ctypes.byref(yd), ctypes.byref(d), buf, 96)
             r["config_moments"] = buf.value.decode()
             r["moments_rc"] = lib.mi355_conv3d_fwd(ctypes.byref(xd), w.data_ptr(), ctypes.byref(yd), ctypes.byref(d), None)
-            r["moments_launched"] = take()
+            r["moments_launched"], r["moments_geometry"] = take(), geometry()
             res["fwd:" + cid] = r
         finally:
             for k, v in saved.items():
@@ -126,15 +133,19 @@ def main():
         r["config"] = buf.value.decode()
         r["workspace"] = nbytes = lib.mi355_conv3d_wgrad_workspace(ctypes.byref(xd), ctypes.byref(dyd), ctypes.byref(d))
         ws, dw = torch.zeros(max(nbytes // 4, 1)), torch.zeros(1 << 20)
-        take()
+        take(), geometry()
         r["rc"] = lib.mi355_conv3d_wgrad(ctypes.byref(xd), ctypes.byref(dyd), dw.data_ptr(), ctypes.byref(d), ws.data_ptr(), nbytes, None)
-        r["launched"] = take()
+        r["launched"], r["geometry"] = take(), geometry()
         r["short_ws_rc"] = lib.mi355_conv3d_wgrad(ctypes.byref(xd), ctypes.byref(dyd), dw.data_ptr(), ctypes.byref(d), ws.data_ptr(),
                                                   nbytes - 1, None)
         r["short_ws_launched"] = take()
         res["wgrad:" + cid] = r
     be.set_precision("fp32")
-    print(json.dumps(res))
+    return res
+
+
+def main():
+    print(json.dumps(collect()))
 
 
 if __name__ == "__main__":

@@ -36,7 +36,8 @@ if [ ! -f "$here/build/emu.o" ] || [ "$here/emu.cpp" -nt "$here/build/emu.o" ] |
 fi
 if [ "$rebuilt" = 1 ] || [ ! -f "$so" ]; then
   # link beside the target and rename: parallel test workers that call this script never see a half-written library
-  g++ -shared -o "$so.$$" "${objs[@]}" "$here/build/emu.o" -lpthread
+  # --no-undefined: a cross-file declaration that drifted from its definition (csrc/conv_internal.h) fails here, not when the library loads
+  g++ -shared -Wl,--no-undefined -o "$so.$$" "${objs[@]}" "$here/build/emu.o" -lpthread
   mv -f "$so.$$" "$so"
 fi
 echo "built $so"

@@ -46,12 +46,19 @@ void run_block(BlockState& bs) {
 }
 
 static std::mutex g_launch_mu;
-static std::string g_launches;
+static std::string g_launches, g_geometry;
 
 void record_launch(const char* kernel) {
   std::lock_guard<std::mutex> lock(g_launch_mu);
   g_launches += kernel;
   g_launches += '\n';
+}
+
+void record_geometry(emu_dim3 grid, emu_dim3 block, size_t lds_bytes) {
+  char line[128];
+  snprintf(line, sizeof(line), "%u %u %u %u %u %u %zu\n", grid.x, grid.y, grid.z, block.x, block.y, block.z, lds_bytes);
+  std::lock_guard<std::mutex> lock(g_launch_mu);
+  g_geometry += line;
 }
 
 }  // namespace emu
@@ -63,5 +70,15 @@ extern "C" size_t emu_take_launches(char* out, size_t n) {
   const size_t len = emu::g_launches.size();
   if (out && n) snprintf(out, n, "%s", emu::g_launches.c_str());
   emu::g_launches.clear();
+  return len;
+}
+
+// The geometry of the same launches, one line each ("gx gy gz bx by bz lds_bytes"), read and cleared like emu_take_launches and
+// independently of it.
+extern "C" size_t emu_take_geometry(char* out, size_t n) {
+  std::lock_guard<std::mutex> lock(emu::g_launch_mu);
+  const size_t len = emu::g_geometry.size();
+  if (out && n) snprintf(out, n, "%s", emu::g_geometry.c_str());
+  emu::g_geometry.clear();
   return len;
 }

@@ -123,10 +123,13 @@ void run_block(BlockState& bs);
 // the kernel expression of every LAUNCH, in order (read and cleared by emu_take_launches in emu.cpp): tests check that a config query
 // names the kernel the entry point launches
 void record_launch(const char* kernel);
+// ... and beside it, one line per launch: grid x y z, block x y z, dynamic LDS bytes (read and cleared by emu_take_geometry): the pinned
+// launch geometry of tests/golden/conv_launch_geometry.json
+void record_geometry(emu_dim3 grid, emu_dim3 block, size_t lds_bytes);
 
 template <class F>
 void launch(emu_dim3 grid, emu_dim3 block, size_t lds_bytes, F body, const char* kernel = nullptr) {
-  if (kernel) record_launch(kernel);
+  if (kernel) { record_launch(kernel); record_geometry(grid, block, lds_bytes); }
   // MI355_EMU_NOEXEC=1: a launch returns at once (tools/host_enqueue.py times the host side of a step -- Python, ctypes, the C dispatch --
   // at the real shapes without a GPU; outputs are garbage, nothing may check them)
   static const bool noexec = [] { const char* v = getenv("MI355_EMU_NOEXEC"); return v && v[0] == '1'; }();
