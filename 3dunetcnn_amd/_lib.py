@@ -172,7 +172,14 @@ SIGNATURES = {
     "mi355_zscore_select": (ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int64, c_int32, c_float, c_int32, c_int32, c_int32, c_void_p,
                                            c_void_p, c_void_p]),
     "mi355_threshold_any": (ctypes.c_int, [c_void_p, c_int32, c_int64, c_void_p, c_void_p, c_void_p]),
+    "mi355_permute3d": (ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, POINTER(c_int32), c_int32,
+                                       c_void_p]),
+    "mi355_unpermute_accumulate": (ctypes.c_int, [c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, POINTER(c_int32),
+                                                  c_int32, c_int32, c_float, c_int32, c_void_p]),
 }
+PERMUTE_MAX_BATCH = 64             # MI355_PERMUTE_MAX_BATCH: samples with a code of their own per call of mi355_permute3d / _unpermute_accumulate
+PERMUTE_TILE = 64                  # MI355_PERMUTE_TILE: edge of the LDS tile of the route on which W moves
+ACT_NONE, ACT_SIGMOID, ACT_SOFTMAX = 0, 1, 2                    # MI355_ACT_NONE / _SIGMOID / _SOFTMAX (mi355_unpermute_accumulate)
 SURFACE_SCRATCH_BYTES = 32832      # MI355_SURFACE_SCRATCH_BYTES of the header: scratch of mi355_surface_stats, per channel
 FOCAL_SCRATCH_BYTES = 4096         # MI355_FOCAL_SCRATCH_BYTES of the header: the block partials of mi355_focal_fwd_bwd
 PERCENTILE_MAX_Q = 4               # MI355_PERCENTILE_MAX_Q: percentiles per call of mi355_percentiles

@@ -902,6 +902,44 @@ class Backend:
               "threshold_any")
         return out
 
+    # -- signed axis permutations and the permutation-ensemble fold (csrc/permute.hip) ---------------------------------------------------
+    @staticmethod
+    def _perm_codes(codes, n):
+        codes = [int(v) for v in codes]
+        assert len(codes) in (1, n), f"{len(codes)} codes for {n} samples"
+        return codes, (ctypes.c_int32 * len(codes))(*codes)
+
+    def permute3d(self, x, codes):
+        """x [N, C, D, H, W], dense, elements of 1, 2 or 4 bytes; codes: one code (see mi355_permute3d) for every sample or one per sample
+        (N <= _lib.PERMUTE_MAX_BATCH), all with the same output extents. Returns the permuted batch: a bit copy, one launch."""
+        assert x.is_contiguous() and x.dim() == 5 and x.element_size() in (1, 2, 4)
+        n, c, d, h, w = x.shape
+        codes, arr = self._perm_codes(codes, n)
+        out = torch.empty((n, c) + tuple(x.shape[2 + ((codes[0] >> (2 * a)) & 3)] for a in range(3)), dtype=x.dtype, device=x.device)
+        check(self.lib.mi355_permute3d(x.data_ptr(), out.data_ptr(), n, c, d, h, w, x.element_size(), arr, len(codes), self.stream()),
+              "permute3d")
+        return out
+
+    def unpermute_accumulate(self, src, codes, acc=None, activation=None, weight=1.0, init=None):
+        """src [N, C, ...] fp32 / bf16 / fp16: predictions of a batch that was permuted with `codes`. acc fp32 [N, C, D, H, W] in the
+        un-permuted extents, or None (allocated, init implied): acc = (init ? 0 : acc) + weight * activation(src) read back through the
+        inverse permutation; activation None | "sigmoid" | "softmax" (over C <= 16). One launch. Returns acc."""
+        assert src.is_contiguous() and src.dim() == 5 and src.dtype in (torch.float32, torch.bfloat16, torch.float16)
+        n, c = src.shape[:2]
+        codes, arr = self._perm_codes(codes, n)
+        dhw = [0, 0, 0]
+        for a in range(3):
+            dhw[(codes[0] >> (2 * a)) & 3] = int(src.shape[2 + a])
+        if acc is None:
+            assert init is None or init
+            acc, init = torch.empty((n, c) + tuple(dhw), dtype=torch.float32, device=src.device), True
+        assert acc.is_contiguous() and acc.dtype == torch.float32 and tuple(acc.shape) == (n, c) + tuple(dhw) and acc.device == src.device
+        elem = {torch.float32: _lib.ACT_F32, torch.bfloat16: _lib.ACT_BF16, torch.float16: _lib.ACT_F16}[src.dtype]
+        act = {None: _lib.ACT_NONE, "none": _lib.ACT_NONE, "sigmoid": _lib.ACT_SIGMOID, "softmax": _lib.ACT_SOFTMAX}[activation]
+        check(self.lib.mi355_unpermute_accumulate(src.data_ptr(), elem, acc.data_ptr(), n, c, dhw[0], dhw[1], dhw[2], arr, len(codes), act,
+                                                  float(weight), int(bool(init)), self.stream()), "unpermute_accumulate")
+        return acc
+
     def augment_batch(self, image, label, matrices, gain=None, offset=None, out_shape=None, padding="border", normalize=False):
         """Training augmentation of a batch in two launches (mi355_augment_batch). image [N, Ci, D, H, W] fp32; label None or
         [N, Cl, D, H, W] uint8 / fp32; matrices [N, 3, 4] (or [N, 12]) fp32 ON THE DEVICE: output voxel -> source voxel, (z, y, x)

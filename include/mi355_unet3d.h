@@ -618,6 +618,44 @@ int mi355_zscore_select(const float* x, float* y, int32_t c, int64_t voxels, int
                         int32_t zero_std_to_one, int32_t* n, void* scratch, void* stream);
 int mi355_threshold_any(const float* x, int32_t c, int64_t voxels, const float* thr, uint8_t* out, void* stream);
 
+/* ---- signed axis permutations and the permutation-ensemble fold (csrc/permute.hip) ---------------------------------------------------
+ * The 48 rotations and reflections of a volume (the reference's unet3d/utils/augment.py: permute_data, reverse_permute_data), each as one
+ * pass, for a batch [n][c][d][h][w] that is already on the device. 1 <= c <= 65535, 1 <= n <= 65535, 1 <= d*h*w <= 2^31 - 2; element
+ * offsets are 64-bit. Neither function takes scratch. No atomics: one thread owns one output voxel, two calls give the same bits.
+ *
+ * A signed axis permutation is written as a CODE, one int: s0 | s1 << 2 | s2 << 4 | f0 << 6 | f1 << 7 | f2 << 8.
+ *   s_a in {0, 1, 2} is the source axis (0 = D, 1 = H, 2 = W) that output axis a reads; (s0, s1, s2) is a permutation.
+ *   f_a: output axis a runs backwards.
+ *   With source extents E: out_extent[a] = E[s_a], and
+ *   out[n, c, v0, v1, v2] = in[n, c, u0, u1, u2] with u[s_a] = f_a ? out_extent[a] - 1 - v_a : v_a.
+ * codes: HOST int32[n_codes], n_codes = 1 (the one code for every sample) or n (one per sample; then n <= MI355_PERMUTE_MAX_BATCH). The
+ *   library checks them on the host and carries them to the kernel in its arguments: no device table, no copy, no wait. All codes of one
+ *   call give the same output extents.
+ *
+ * mi355_permute3d: dst = the permuted src, a bit copy of elements of elem_bytes in {1, 2, 4} (uint8 one-hot labels, int16 label maps,
+ *   fp16 / bf16 activations, fp32, int32). src (extents d, h, w) and dst (the output extents) are distinct, dense buffers. A workgroup
+ *   takes one of two routes: s2 == 2 (rows of W stay rows, possibly reversed): a coalesced copy, 16 bytes per thread where both pointers
+ *   are 16-byte aligned and the row is a whole number of 16-byte groups; W moves: a padded LDS tile of MI355_PERMUTE_TILE squared
+ *   elements in the plane of source W and the axis that becomes output W, read along source W, written along output W. One launch.
+ * mi355_unpermute_accumulate: (d, h, w) are the extents of acc, the UN-PERMUTED fp32 volume [n][c][d][h][w]; src holds [n][c] volumes in
+ *   the extents the FORWARD code makes of them, fp32 (src_elem MI355_ACT_F32) or 16-bit (MI355_ACT_BF16 / MI355_ACT_F16). For every voxel
+ *   u of acc and its image v under the forward code (v_a = f_a ? out_extent[a] - 1 - u[s_a] : u[s_a]):
+ *     acc[n, c, u] = (init ? 0 : acc[n, c, u]) + weight * p[n, c, v]       (init: one product; otherwise one fused multiply-add)
+ *   p = src (MI355_ACT_NONE), 1 / (1 + exp(-src)) (MI355_ACT_SIGMOID) or the softmax over the c channels of that voxel
+ *   (MI355_ACT_SOFTMAX, c <= 16). init != 0 never reads acc: the caller may hand it uninitialised memory. The same two routes. One launch.
+ * MI355_EINVAL, and no launch, for: a null pointer, a non-positive extent, src == dst (src == acc), an elem_bytes / src_elem / activation
+ *   outside its set, a code that is no permutation (or has other bits set), n_codes not in {1, n}, per-sample codes for n above
+ *   MI355_PERMUTE_MAX_BATCH, per-sample codes with different output extents, c > 16 with softmax, a NaN weight. */
+#define MI355_PERMUTE_MAX_BATCH 64
+#define MI355_PERMUTE_TILE 64
+#define MI355_ACT_NONE 0
+#define MI355_ACT_SIGMOID 1
+#define MI355_ACT_SOFTMAX 2
+int mi355_permute3d(const void* src, void* dst, int32_t n, int32_t c, int32_t d, int32_t h, int32_t w, int32_t elem_bytes,
+                    const int32_t* codes, int32_t n_codes, void* stream);
+int mi355_unpermute_accumulate(const void* src, int32_t src_elem, float* acc, int32_t n, int32_t c, int32_t d, int32_t h, int32_t w,
+                               const int32_t* codes, int32_t n_codes, int32_t activation, float weight, int32_t init, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
