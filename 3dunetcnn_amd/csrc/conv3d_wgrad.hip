@@ -16,6 +16,7 @@
 //   conv3d_wgrad_mfma : 3x3x3 stride 2 and 1x1x1 (incl. the depth-to-space transposed-conv form): split-K over voxel tiles staged
 //                       whole in LDS, register-prefetch software pipeline.
 #include "gfx950_dialect.h"
+#include <cstdlib>
 #include "../../include/mi355_unet3d.h"
 #include "act_io.h"
 #include "conv_internal.h"
@@ -377,7 +378,11 @@ __global__ __launch_bounds__(256) void conv3d_wgrad_ring(WgradArgs a) {
 // = 4 ci per thread, 64 float4 per slab), every thread keeps 8 independent running sums so 8 loads are in flight, and the 4
 // slab-groups are combined through LDS in a fixed order. (A thread that walks all slabs with one dependent load at a time is
 // latency-bound: 5 % of the training step at 512 slabs.)
-__global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* ws, float* dw, int Cout, int Cin, int T, int SL, int ciTiles, int parts) {
+//
+// This form scatters its result: dw[((co * Cin + ci) * T + tap] is one dword per (co, ci) at a stride of 4 T bytes, and the T taps of one
+// such run come from T different workgroups at different times -- the L2 never merges them (WRITE_SIZE per launch: 33x the tensor).
+// It runs under MI355_WGRAD_REDUCE_ROWS=0 only, as the A/B partner of wgrad_reduce_kernel below.
+__global__ __launch_bounds__(256) void wgrad_reduce_scatter_kernel(const float* ws, float* dw, int Cout, int Cin, int T, int SL, int ciTiles, int parts) {
   __shared__ float4 part[4][256];
   // parts = 4: four workgroups share one tile (64 float4 each) -- launches with few (pair, tap) tiles are otherwise latency-bound
   const int tile = blockIdx.x / parts, sub0 = (blockIdx.x % parts) * (4 / parts), sub1 = sub0 + 4 / parts;
@@ -428,11 +433,115 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* ws, floa
   }
 }
 
+// The same launch and the same sums with contiguous stores. Within one (co tile, ci tile) pair the result is 32 rows (co) of 32 T floats
+// that are contiguous in dw (ci, then tap); element p = row * 32 T + ci * T + tap of the pair. The T * parts workgroups of the pair cut
+// that range into equal pieces of 1024 / parts consecutive elements -- as many outputs per workgroup as above, other ones.
+//   reads : a work item is one float4 (4 ci of one row and tap) of every slab, walked exactly as above (wave grp takes slabs grp, grp + 4,
+//           ..., 8 rotating sums = 8 loads in flight, the fixed combine); the lanes of a wave take the quads of a row first, then the
+//           taps, so a load instruction covers runs of one 128-byte slab row each. A piece that ends inside a quad reads the whole quad.
+//   LDS   : every wave leaves its sums at the elements' positions in the piece (part[grp][p - P0]).
+//   stores: thread t adds the 4 waves' sums of element t, t + 256, ... in the order 0..3 and stores one dword: a wave writes 256
+//           consecutive bytes (dw is a slice of the flat gradient buffer: 4-byte aligned, no wider store).
+// Every element's additions are those of the scatter form in the same order: the result is bit-identical.
+// Pieces that follow each other in dw share slab rows (a 128-byte row holds 32 ci of ONE tap, a piece holds all taps of ~9 or ~38 ci),
+// so the block index is remapped to give each group of blocks that shares an L2 (blockIdx % 8) a contiguous range of pieces.
+// At most 4 waves per SIMD: 8 sums and 8 loads of 16 bytes in flight need ~80 registers. (Left to aim at 8 waves hipcc fits the kernel into
+// 56 by waiting for every load before it issues the next: the launches with few workgroups and many slabs ran 5x slower than the scatter
+// form, 361 against 65 us for the 4 workgroups of a 1x1x1 32 -> 32 gradient.)
+__global__ __launch_bounds__(256) WAVES_PER_SIMD_RANGE(1, 4) void wgrad_reduce_kernel(const float* ws, float* dw, int Cout, int Cin, int T, int SL, int ciTiles, int parts) {
+  __shared__ float part[4][1024];
+  const int RL = 32 * T, L = 1024 / parts;             // floats per co row of the pair, floats per piece
+  const unsigned G = gridDim.x, q8 = G / 8, r8 = G % 8, lab = blockIdx.x % 8;
+  const unsigned piece = lab * q8 + (lab < r8 ? lab : r8) + blockIdx.x / 8;       // a bijection of [0, G) for any G
+  const int pair = (int)(piece / (unsigned)(T * parts));
+  const int P0 = (int)(piece % (unsigned)(T * parts)) * L;
+  const int cot = pair / ciTiles, cit = pair % ciTiles;
+  const int tid = threadIdx.x, e4 = tid & 63, grp = tid >> 6;
+  const float4* base = reinterpret_cast<const float4*>(ws + (size_t)pair * SL * T * 1024);
+  const size_t slab_stride = (size_t)T * 256;       // in float4
+  // one work item: float4 `quad` of (row, tap) summed over this wave's slabs, left in part[grp] where the piece holds its 4 elements
+  auto item = [&](int row, int tap, int quad) {
+    const int f4 = tap * 256 + row * 8 + quad;
+    float4 acc[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) acc[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+    int k = grp;
+    for (; k + 28 < SL; k += 32) {
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const float4 v = base[(size_t)(k + 4 * u) * slab_stride + f4];
+        acc[u].x += v.x; acc[u].y += v.y; acc[u].z += v.z; acc[u].w += v.w;
+      }
+    }
+    // the tail: at most 7 slabs are left (k + 28 >= SL), slab k + 4 u into sum u as in the scatter form's loop -- unrolled, so the
+    // sums stay in registers (indexed by a loop counter they live in scratch memory). The loads are unconditional and go out together
+    // (behind a branch each waits for the one before): a slab past the end reads slab 0 instead and is not added.
+    float4 tv[7];
+#pragma unroll
+    for (int u = 0; u < 7; ++u) tv[u] = base[(size_t)(k + 4 * u < SL ? k + 4 * u : 0) * slab_stride + f4];
+#pragma unroll
+    for (int u = 0; u < 7; ++u) {
+      if (k + 4 * u < SL) { acc[u].x += tv[u].x; acc[u].y += tv[u].y; acc[u].z += tv[u].z; acc[u].w += tv[u].w; }
+    }
+    float4 s = acc[0];
+#pragma unroll
+    for (int u = 1; u < 8; ++u) { s.x += acc[u].x; s.y += acc[u].y; s.z += acc[u].z; s.w += acc[u].w; }
+    const int o = row * RL + 4 * quad * T + tap - P0;
+    const float v[4] = {s.x, s.y, s.z, s.w};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int oe = o + e * T;
+      if (oe >= 0 && oe < L) part[grp][oe] = v[e];
+    }
+  };
+  if (L % RL == 0) {
+    // whole rows (T = 1): L / 4 items, none read in vain
+    const int r0 = P0 / RL;
+    for (int i = e4; i < L / 4; i += 64) {
+      const int rem = i % (8 * T);
+      item(r0 + i / (8 * T), rem / 8, rem % 8);
+    }
+  } else {
+    // the piece's part [ja, jb) of row `row` lies in quads qa .. qa + qn - 1; the items of all its rows are dealt to the lanes as one list
+    const int r0 = P0 / RL, r1 = (P0 + L - 1) / RL;
+    auto quads = [&](int row, int& qa) {
+      const int ja = P0 > row * RL ? P0 - row * RL : 0, jb = P0 + L < (row + 1) * RL ? P0 + L - row * RL : RL;
+      qa = (ja / T) / 4;
+      return ((jb - 1) / T) / 4 - qa + 1;
+    };
+    int total = 0, qa;
+    for (int row = r0; row <= r1; ++row) total += quads(row, qa) * T;
+    for (int i = e4; i < total; i += 64) {
+      int row = r0, rem = i, qn;
+      for (;; ++row) {
+        qn = quads(row, qa);
+        if (rem < qn * T) break;
+        rem -= qn * T;
+      }
+      item(row, rem / qn, qa + rem % qn);
+    }
+  }
+  __syncthreads();
+  for (int o = tid; o < L; o += 256) {
+    float s = part[0][o];
+#pragma unroll
+    for (int g = 1; g < 4; ++g) s += part[g][o];
+    const int row = (P0 + o) / RL, j = (P0 + o) % RL;
+    if (cot * 32 + row < Cout && cit * 32 + j / T < Cin) dw[((size_t)(cot * 32 + row) * Cin + cit * 32) * T + j] = s;
+  }
+}
+
+// MI355_WGRAD_REDUCE_ROWS=0: the scatter form (the A/B switch; read at every call, the tests flip it)
+static bool wgrad_reduce_rows() { const char* v = getenv("MI355_WGRAD_REDUCE_ROWS"); return !(v && v[0] == '0'); }
+
 int mi355_wgrad_reduce_launch(const float* ws, float* dw, int Cout, int Cin, int T, int SL, int ciTiles, void* stream) {
   const int coTiles = ceil_div(Cout, 32);
   const long long tiles = (long long)coTiles * ciTiles * T;
   const int parts = tiles < 256 ? 4 : 1;
-  LAUNCH(wgrad_reduce_kernel, dim3((unsigned)(tiles * parts)), dim3(256), 0, stream, ws, dw, Cout, Cin, T, SL, ciTiles, parts);
+  if (wgrad_reduce_rows())
+    LAUNCH(wgrad_reduce_kernel, dim3((unsigned)(tiles * parts)), dim3(256), 0, stream, ws, dw, Cout, Cin, T, SL, ciTiles, parts);
+  else
+    LAUNCH(wgrad_reduce_scatter_kernel, dim3((unsigned)(tiles * parts)), dim3(256), 0, stream, ws, dw, Cout, Cin, T, SL, ciTiles, parts);
   return LAUNCH_CHECK();
 }
 

@@ -21,6 +21,9 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define DYN_LDS(name) extern __shared__ __attribute__((aligned(16))) float name[]
 // register budget: the allocator must fit at least n waves per SIMD (512 unified registers / n, accumulators included)
 #define MIN_WAVES_PER_SIMD(n) __attribute__((amdgpu_waves_per_eu(n)))
+// ... and no more than hi: the registers of 512 / hi are the kernel's to use (a streaming kernel that wants many loads in flight per lane:
+// aiming at 8 waves per SIMD, hipcc keeps it under 64 registers by waiting for every load before it issues the next)
+#define WAVES_PER_SIMD_RANGE(lo, hi) __attribute__((amdgpu_waves_per_eu(lo, hi)))
 // exactly one wave per SIMD: the wave owns a lane's whole 512-entry register file (256 architectural VGPRs + 256 AGPRs)
 #define ONE_WAVE_PER_SIMD __attribute__((amdgpu_waves_per_eu(1, 1)))
 // keep a value in the accumulation half of the register file from here on (an MFMA reads its A / B operands from AGPRs directly; without

@@ -161,6 +161,10 @@ __global__ __launch_bounds__(256) void upsample2x_fwd_rows_kernel(const T* lo, i
 
 // (The backward pass was measured in the same form and did not move -- 64 loads per coarse voxel bound it, not the index arithmetic; it keeps
 // the grid-stride kernel above with its weights hoisted: 0.435 -> 0.381 ms over the three launches of the fp32 step, 0.499 -> 0.382 in bf16.)
+// (A tile form was measured too: a 4 x 4 x 4 coarse tile x 4 channel runs per workgroup, the 10^3 fine region staged once in 62.5 KiB of LDS,
+// the same 64 terms per coarse voxel read from there -- same bits, 1.95x the tensor fetched instead of ~4x, and slower: 312 -> 457 us on the
+// 128^3 level, 79 -> 112 on 64^3. Two workgroups per CU, a barrier between staging and use, and 64 LDS reads of 16 bytes per coarse voxel
+// in place of 64 cached loads: not in the tree, profiles/wgrad_reduce_rows.txt.)
 
 // rows form: a 256-thread block holds whole voxels of Q channel runs and the row count fits an int; MI355_UPSAMPLE_ROWS=0 (read once): never
 static bool upsample_rows_ok(int Q, long long rows) {
@@ -218,6 +222,9 @@ extern "C" int mi355_upsample2x_bwd(const mi355_act* dcat, const mi355_act* dlo,
 }
 
 // ---- layout ------------------------------------------------------------------------------------
+// (The 4-channel network input writes 4x its size: one 4-byte store per element into 16-byte voxel rows whose other elements come from other
+// workgroups later. A form with one voxel row per thread -- gather the 4 planes, one 16-byte store -- ran 61 -> 30 us per launch and did not
+// move the step, 51.13 ms with and without it: not in the tree, profiles/wgrad_reduce_rows.txt.)
 template <typename T>
 __global__ void ncdhw_to_ndhwc_kernel(const float* src, T* dst, int dld, int N, int C, long long V) {
   const long long total = (long long)N * V * C;

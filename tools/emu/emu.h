@@ -339,6 +339,7 @@ static inline unsigned long long atomicMax(unsigned long long* p, unsigned long 
 #define SET_MAX_DYN_LDS(kernel, bytes) do {} while (0)
 #define SCHED_BARRIER() do {} while (0)
 #define MIN_WAVES_PER_SIMD(n)
+#define WAVES_PER_SIMD_RANGE(lo, hi)
 #define ONE_WAVE_PER_SIMD
 #define PIN_IN_AGPR(v) ((void)0)
 #define PIN_IN_VGPR(v) ((void)0)
