@@ -101,6 +101,10 @@ SIGNATURES = {
     "mi355_proj_workspace": (c_size_t, [POINTER(MiAct), c_int32]),
     "mi355_proj_bwd": (ctypes.c_int, [POINTER(MiAct), c_void_p, c_void_p, c_float, c_void_p, c_void_p, POINTER(MiAct), c_void_p, c_void_p, c_int32,
                                       c_void_p, c_size_t, c_void_p]),
+    "mi355_ds_head_scratch_bytes": (c_size_t, [POINTER(MiAct), c_int32]),
+    "mi355_ds_head_fwd": (ctypes.c_int, [POINTER(MiAct), c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
+    "mi355_ds_head_bwd": (ctypes.c_int, [POINTER(MiAct), c_void_p, c_void_p, c_float, c_void_p, c_void_p, POINTER(MiAct), c_void_p, c_void_p, c_int32,
+                                         c_int32, c_void_p, c_size_t, c_void_p]),
     "mi355_sw_accumulate": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
                                            c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "mi355_sw_gather": (ctypes.c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32, c_int32, c_int32,

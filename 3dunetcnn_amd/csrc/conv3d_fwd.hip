@@ -772,12 +772,14 @@ static FwdPlan plan_fwd(const mi355_act* x, const mi355_act* y, const mi355_conv
   return p;
 }
 
-// the forms that exist for 16-bit activation storage: what a UNet3D with activation_storage="bf16" sends here (the 3x3x3 stride-1
-// convolutions of that network run on the 16-bit-operand kernels of conv3d_bf16*.hip): 1x1x1 on a plain input, 3x3x3 stride 2 on a plain
-// input (with or without the moments epilogue), and the zero-insert form (stride-2 dgrad, ConvTranspose3d(k3, s2))
+// the forms that exist for 16-bit activation storage: what a UNet3D or a DynUNet with 16-bit activation storage sends here (their 3x3x3
+// stride-1 convolutions run on the 16-bit-operand kernels of conv3d_bf16*.hip): 1x1x1 on a plain, normalised or space-to-depth input
+// (DynUNet's ConvTranspose3d(k2, s2) and its data gradient), 3x3x3 stride 2 on a plain or normalised input (with or without the moments
+// epilogue), and the zero-insert form (stride-2 dgrad, ConvTranspose3d(k3, s2))
 template <typename TA> constexpr bool act_form_exists(int kd, int stride, int im, int fuse) {
-  return std::is_same<TA, float>::value || (kd == 1 && im == MI355_IN_PLAIN && fuse == 0) ||
-         (kd == 3 && stride == 2 && im == MI355_IN_PLAIN && fuse <= 1) || (kd == 3 && im == MI355_IN_ZERO_INSERT && fuse == 0);
+  return std::is_same<TA, float>::value || (kd == 1 && im != MI355_IN_ZERO_INSERT && fuse == 0) ||
+         (kd == 3 && stride == 2 && (im == MI355_IN_PLAIN || im == MI355_IN_AFFINE_ACT) && fuse <= 1) ||
+         (kd == 3 && im == MI355_IN_ZERO_INSERT && fuse == 0);
 }
 
 template <int KD, int STRIDE, int TZ, int TY, int TX, int KC, int PADV, int WM, int WN, int MT, int NT, typename TA = float>

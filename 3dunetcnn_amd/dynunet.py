@@ -115,7 +115,8 @@ class HipDynUNet(HipNetBase):
             bad.append("activation other than LeakyReLU(0.01)")
         if bad:
             raise NotImplementedError("HipDynUNet implements the configuration the reference ships (brats2020_config.json); "
-                                      "unsupported: " + ", ".join(bad))
+                                      "unsupported: " + ", ".join(bad)
+                                      + (" (deep supervision: HipDynUNetDS, same arguments)" if deep_supervision else ""))
         L = len(strides)
         if filters is None:
             filters = [min(2 ** (5 + i), 320) for i in range(L)]     # MONAI default for spatial_dims == 3
@@ -162,6 +163,8 @@ class HipDynUNet(HipNetBase):
             out.append((prefix + ".downsample", downs[depth][0]))
             walk(prefix + ".next_layer", depth + 1)
             out.append((prefix + ".upsample", ups[depth][0]))
+            if 1 <= depth <= len(self.deep_supervision_heads):        # DynUNetSkipLayer.super_head: the head of this depth (HipDynUNetDS)
+                out.append((prefix + ".super_head", f"deep_supervision_heads.{depth - 1}"))
         walk("skip_layers", 0)
         return out                                   # [(alias prefix, canonical prefix)]
 
@@ -180,6 +183,17 @@ class HipDynUNet(HipNetBase):
 
     def forward(self, x):
         return self._run(x)
+
+    def _supervised(self):
+        """Heads this forward evaluates (HipDynUNetDS in training mode); 0: the logits alone."""
+        return 0
+
+    def _prepare_dout(self, dout):
+        """The stacked output's gradient [N, 1 + K, ...] in the order of the buffer the forward wrote, [1 + K][N]...: no copy when it
+        already has that order (HipDeepSupervisionLoss returns it so), one otherwise."""
+        if dout.dim() == 6:
+            return dout.transpose(0, 1).contiguous()
+        return dout.contiguous()
 
     # ---- forward -------------------------------------------------------------------------------------------------------
     def _blocks(self):
@@ -220,11 +234,14 @@ class HipDynUNet(HipNetBase):
                                  "(ConvTranspose3d(k2,s2) output must match the skip, as in MONAI DynUNet)")
             sizes.append(tuple(s // 2 for s in sizes[-1]))
         cpad = (self.in_channels + 3) // 4 * 4
+        # the network input stays fp32 when it has the first-layer kernels' 4 channels (they read fp32 and store either type), as in
+        # HipUNet3D; wider inputs are stored like every other activation
+        xa_dtype = torch.float32 if cpad == 4 else be.act_dtype
         if cpad == self.in_channels:
-            xa = be.empty_act(n, D, H, W, self.in_channels)
+            xa = be.empty_act(n, D, H, W, self.in_channels, dtype=xa_dtype)
             be.ncdhw_to_ndhwc(x, xa)
         else:
-            xa = be.zeros_act(n, D, H, W, cpad)
+            xa = be.zeros_act(n, D, H, W, cpad, dtype=xa_dtype)
             be.ncdhw_to_ndhwc(x, xa.slice(0, self.in_channels))
         cats = [be.empty_act(n, *sizes[i], 2 * f[i]) for i in range(L - 1)]
         enc = []
@@ -236,6 +253,9 @@ class HipDynUNet(HipNetBase):
             cur = _In(s["r2"], s["st2"][1], s["st2"][2])
         ups = []
         ones = zeros = None
+        # deep supervision: the logits and the K head outputs are slots of one buffer [1 + K][N][C][D][H][W]
+        K = self._supervised()
+        stack = torch.empty(1 + K, n, self.out_channels, D, H, W, dtype=torch.float32, device=x.device) if K else None
         for k, up in enumerate(self.upsamples):
             lvl = L - 2 - k
             co = f[lvl]
@@ -254,12 +274,16 @@ class HipDynUNet(HipNetBase):
             s["tin"] = cur
             ups.append(s)
             cur = _In(s["r2"], s["st2"][1], s["st2"][2])
-        logits = torch.empty(n, self.out_channels, D, H, W, dtype=torch.float32, device=x.device)
+            if 1 <= lvl <= K:                 # head lvl - 1 reads this level's activated output: raw + its norm prologue
+                hd = self.deep_supervision_heads[lvl - 1].conv.conv
+                be.ds_head_fwd(cur.act, hd.weight.data.reshape(self.out_channels, -1), hd.bias.data, stack[lvl], 2 ** lvl, cur.scale, cur.shift,
+                               SLOPE)
+        logits = stack[0] if K else torch.empty(n, self.out_channels, D, H, W, dtype=torch.float32, device=x.device)
         ob = self.output_block.conv.conv
         be.proj_fwd(cur.act, ob.weight.data.reshape(self.out_channels, -1), ob.bias.data, logits, cur.scale, cur.shift, SLOPE)
         self._end_forward()
-        saved = dict(enc=enc, ups=ups, sizes=sizes, n=n, last=cur) if keep else None
-        return logits, saved
+        saved = dict(enc=enc, ups=ups, sizes=sizes, n=n, last=cur, heads=K) if keep else None
+        return (stack.transpose(0, 1) if K else logits), saved       # [N, 1 + K, C, D, H, W]: every out[:, l] contiguous
 
     # ---- backward ------------------------------------------------------------------------------------------------------
     def _block_bwd(self, be, blk, s, dA2, need_dx, dx_residual=None):
@@ -290,7 +314,7 @@ class HipDynUNet(HipNetBase):
         if not need_dx:
             return None
         n, d, h, w, cin = xin.act.shape
-        dAin = be.empty_act(n, d, h, w, cin)
+        dAin = be.empty_act(n, d, h, w, cin, dtype=xin.act.dtype)          # a tensor's gradient is stored like the tensor
         wp = self._packed_weight(blk.conv1.conv.weight, 1, self._ci_pad(blk, cin))
         if blk.stride == 1:
             be.conv_fwd(d_r1, wp, dAin, 3, 1, residual=dx_residual)
@@ -302,6 +326,16 @@ class HipDynUNet(HipNetBase):
         f, L = self.filters, len(self.filters)
         enc, ups, n = saved["enc"], saved["ups"], saved["n"]
         last = saved["last"]
+        K = saved["heads"]
+        dstack = dlogits if K else None      # [1 + K][N][C][D][H][W] (_prepare_dout)
+        if K:
+            dlogits = dstack[0]
+        for head in self.deep_supervision_heads[K:]:
+            # heads this forward did not evaluate (eval mode with grad): no kernel writes their slices of the persistent gradient
+            # buffer, which would otherwise still hold an earlier step's values. Their gradient is zero, as autograd's is for MONAI's
+            hd = head.conv.conv
+            self._gslice(hd.weight).zero_()
+            self._gslice(hd.bias).zero_()
         ob = self.output_block.conv.conv
         dA = be.empty_act(*last.act.shape)
         be.proj_bwd(last.act, ob.weight.data.reshape(self.out_channels, -1), dlogits, dA,
@@ -312,6 +346,13 @@ class HipDynUNet(HipNetBase):
             co = f[lvl]
             up = self.upsamples[k]
             s = ups[k]
+            if 1 <= lvl <= K:
+                # dA holds the gradient from the finer up block; the head adds its own before this level's norm backward consumes the sum.
+                # On the launch stream, not the weight-gradient side stream: the kernel that writes dw / dbias is the one that adds to dA
+                hd = self.deep_supervision_heads[lvl - 1].conv.conv
+                be.ds_head_bwd(s["r2"], hd.weight.data.reshape(self.out_channels, -1), dstack[lvl], dA,
+                               self._gslice(hd.weight).view(self.out_channels, -1), self._gslice(hd.bias), 2 ** lvl, s["st2"][1], s["st2"][2],
+                               SLOPE)
             dcat = self._block_bwd(be, up.conv_block, s, dA, True)
             d_up, d_skip[lvl] = dcat.slice(0, co), dcat.slice(co, co)
             tin = s["tin"]                                  # activated input of the transposed conv (raw + prologue)
@@ -337,3 +378,56 @@ class HipDynUNet(HipNetBase):
             dx_t = torch.empty(n, self.in_channels, *sizes[0], dtype=torch.float32, device=dlogits.device)
             be.ndhwc_to_ncdhw(dx.slice(0, self.in_channels), dx_t)
         return dx_t
+
+
+class HipDynUNetDS(HipDynUNet):
+    """HipDynUNet with MONAI's deep supervision (the nnU-Net training form). [MONAI-memory, parity unpinned: MONAI is not installed here
+    and the reference holds no fixture for the model; the structure follows MONAI >= 1.2 `dynunet.py` as restated in
+    tests/deep_supervision_cases.py, like oracle/dynunet_ref.py for the plain model.]
+
+      deep_supervision_heads = ModuleList(UnetOutBlock(filters[i + 1], out_channels) for i in range(deep_supr_num)),
+                               1 <= deep_supr_num < len(strides) - 1; kaiming_normal_(a=0.01) weights, zero biases
+      head i reads the activated output of the up block at level i + 1 (resolution input / 2^(i + 1))
+      training mode: torch.stack([out] + [F.interpolate(head_i, out.shape[2:]) for i], dim=1)     -> [N, 1 + K, C, D, H, W]
+                     (interpolation "nearest": source index floor(dst / 2^(i + 1)))
+      eval mode:     `out` alone; the heads are not evaluated
+      state dict:    deep_supervision_heads.{i}.conv.conv.{weight,bias} after output_block.*; each DynUNetSkipLayer of depth i + 1 registers
+                     the same module again as `super_head` (after downsample, next_layer, upsample)
+
+    With deep_supervision=False this is HipDynUNet. MI355X execution: the logits and the K head outputs are slots of ONE buffer
+    [1 + K][N][C][D][H][W], returned as its transpose(0, 1) view; slot 0 is written by mi355_proj_fwd, slot 1 + i by mi355_ds_head_fwd
+    (projection + nearest up-sampling in one launch, csrc/deep_supervision.hip). Backward: mi355_ds_head_bwd pools the slot's gradient,
+    writes the head's dw / dbias and adds wT dz to the level's gradient before that level's norm backward reads it. Pair it with
+    losses.HipDeepSupervisionLoss, which returns its gradient in the buffer's order (no copy)."""
+
+    def __init__(self, spatial_dims, in_channels, out_channels, kernel_size, strides, upsample_kernel_size, filters=None,
+                 dropout=None, norm_name=("INSTANCE", {"affine": True}),
+                 act_name=("leakyrelu", {"inplace": True, "negative_slope": 0.01}), deep_supervision=False, deep_supr_num=1,
+                 res_block=False, trans_bias=False):
+        super().__init__(spatial_dims, in_channels, out_channels, kernel_size, strides, upsample_kernel_size, filters=filters, dropout=dropout,
+                         norm_name=norm_name, act_name=act_name, deep_supervision=False, deep_supr_num=deep_supr_num, res_block=res_block,
+                         trans_bias=trans_bias)
+        self.deep_supr_num = deep_supr_num
+        if not deep_supervision:
+            return
+        L = len(self.filters)
+        if not 1 <= deep_supr_num < L - 1:             # MONAI: "deep_supr_num should be less than the number of up sample layers."
+            raise ValueError(f"deep_supr_num should be at least 1 and less than the number of up sample layers ({L - 1}), got {deep_supr_num}")
+        if any(self.filters[i + 1] > 320 for i in range(deep_supr_num)):
+            raise NotImplementedError("deep-supervision heads read at most 320 channels (filters[1 .. deep_supr_num] <= 320)")
+        self.deep_supervision = True
+        for i in range(deep_supr_num):
+            head = _OutBlock(self.filters[i + 1], out_channels)
+            nn.init.kaiming_normal_(head.conv.conv.weight, a=0.01)
+            nn.init.constant_(head.conv.conv.bias, 0)
+            self.deep_supervision_heads.append(head)
+
+    def _supervised(self):
+        return self.deep_supr_num if self.deep_supervision and self.training else 0
+
+    def forward(self, x):
+        K = self._supervised()
+        if K and x.dim() == 5 and x.shape[0] == 0:
+            self._check_input(x)                       # empty batch: the matching empty stack, linked to the parameters (engine._run)
+            return x.new_zeros((0, 1 + K, self.out_channels) + tuple(x.shape[2:])) + sum(p.sum() * 0 for p in self._params())
+        return self._run(x)

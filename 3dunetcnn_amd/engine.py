@@ -35,7 +35,7 @@ class _NetFunction(torch.autograd.Function):
             # the saved activations are released by the first backward (12 GB at 128^3, batch 2): there is no retain_graph form
             raise RuntimeError(f"{type(model).__name__}: backward called a second time through the same forward (or after a no-grad "
                                "forward): the saved activations are freed by the first backward; run the forward again")
-        grads, dx = model._backward_impl(ctx.saved, dlogits.contiguous(), ctx.x_requires_grad)
+        grads, dx = model._backward_impl(ctx.saved, model._prepare_dout(dlogits), ctx.x_requires_grad)
         ctx.saved = None
         return (None, dx) + (None,) * len(grads)   # parameter .grad is set by _backward_impl (zero-copy views of the flat buffer)
 
@@ -264,6 +264,10 @@ class HipNetBase(nn.Module):
             self._be.precision = self._saved_precision
             self._be.act_dtype = self._saved_act_dtype
         self._forward_open = False
+
+    def _prepare_dout(self, dout):
+        """The output's gradient in the memory order _backward_impl_body reads (a network with a strided output overrides this)."""
+        return dout.contiguous()
 
     def _grad_views(self, gbuf, ps):
         """id(parameter) -> its slice of the gradient buffer `gbuf`, shaped like the parameter. The views of the engine's own flat

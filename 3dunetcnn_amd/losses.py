@@ -146,12 +146,26 @@ def _on_device(cw, logits):
 
 
 # ---- autograd ---------------------------------------------------------------------------------------------------------------------------
+def _leave(ctx, dlogits):
+    """A fused-pass loss's forward leaves its UNSCALED d(loss)/d(logits) (or None: no gradient wanted) on its autograd node. This and
+    `_take` are the one place that names where: `_scaled` (the node's own backward) and `_StackedFunction` (which scales it by
+    w_l x upstream straight into the stack's slot) both read it through `_take`."""
+    ctx.dlogits = dlogits
+
+
+def _take(ctx):
+    """The gradient `_leave` stored, released: None when the node holds none (another kind of node, or already taken)."""
+    d = getattr(ctx, "dlogits", None)
+    if d is not None:
+        ctx.dlogits = None
+    return d
+
+
 def _scaled(ctx, g):
     """d(loss)/d(logits) computed by the forward pass, times the incoming scalar gradient -- in place (no second logits-sized tensor)."""
-    d = ctx.dlogits
+    d = _take(ctx)
     if d is None:
         raise RuntimeError("loss backward called a second time: d(loss)/d(logits) is released by the first backward")
-    ctx.dlogits = None
     return d.mul_(g)
 
 
@@ -163,7 +177,7 @@ class _DiceFunction(torch.autograd.Function):
         loss, dlogits = be.dice(logits.contiguous(), target.contiguous(), sigmoid=mod.sigmoid, batch=mod.batch,
                                 squared_pred=mod.squared_pred, smooth_nr=mod.smooth_nr, smooth_dr=mod.smooth_dr, want_grad=want,
                                 generalized=mod.generalized, include_background=mod.include_background)
-        ctx.dlogits = dlogits
+        _leave(ctx, dlogits)
         return loss.reshape(())
 
     @staticmethod
@@ -241,7 +255,7 @@ class _CEFunction(torch.autograd.Function):
                 w *= logits.shape[0] * logits[0, 0].numel() * (1 if mod.ce_mode == "softmax" else c)
             loss, dlogits = be.cross_entropy(logits, target, mode=mod.ce_mode, weight=w, loss=loss,
                                              dlogits=dlogits if want else None, want_grad=want)
-        ctx.dlogits = dlogits
+        _leave(ctx, dlogits)
         return loss.reshape(())
 
     @staticmethod
@@ -276,7 +290,7 @@ class _DiceFocalFunction(torch.autograd.Function):
             loss, dlogits = be.focal(logits, target, mode="softmax" if mod.focal_softmax else "sigmoid", gamma=mod.gamma, alpha=mod.alpha,
                                      include_background=mod.include_background, reduction=mod.reduction, class_weight=cw,
                                      weight=mod.lambda_focal, loss=loss, dlogits=dlogits if want else None, want_grad=want)
-        ctx.dlogits = dlogits
+        _leave(ctx, dlogits)
         return loss.reshape(())
 
     @staticmethod
@@ -490,3 +504,101 @@ class HipDiceFocalLoss(_ClassWeighted):
 
     def forward(self, input, target):
         return _focal_forward(self, input, target)
+
+
+# ---- deep supervision -------------------------------------------------------------------------------------------------------------------
+class _StackedFunction(torch.autograd.Function):
+    """sum_l w_l * loss(stacked[:, l], target) on a stacked output [N, L, C, ...]. The gradient is assembled in the STACK's memory order
+    ([L][N][C]..., returned as its transpose(0, 1) view): HipDynUNetDS's backward reads that buffer as it is. Each level costs the one
+    pass over its gradient that the single-output losses spend on the upstream factor (_scaled): here it scales by w_l x upstream and
+    writes the level's slot. Nothing reads the device on the host; every shape is fixed by the input's."""
+    @staticmethod
+    def forward(ctx, stacked, target, mod, weights):
+        want = ctx.needs_input_grad[0]
+        levels, total = [], None
+        for l, w in enumerate(weights):
+            with torch.enable_grad():
+                xl = stacked[:, l].detach().requires_grad_(want)
+                ll = mod.loss(xl, target)
+            if ll.dim() != 0:
+                raise NotImplementedError("HipDeepSupervisionLoss needs a criterion that returns a scalar (reduction 'mean' or 'sum')")
+            levels.append((xl, ll, w))
+            term = ll.detach() * w
+            total = term if total is None else total + term
+        ctx.levels = levels if want else None
+        ctx.stack_shape = tuple(stacked.shape)
+        return total
+
+    @staticmethod
+    def backward(ctx, g):
+        levels = ctx.levels
+        if levels is None:
+            raise RuntimeError("loss backward called a second time: the per-level gradients are released by the first backward")
+        ctx.levels = None
+        shape = ctx.stack_shape
+        xl0 = levels[0][0]
+        gbuf = torch.empty((shape[1], shape[0]) + shape[2:], dtype=torch.float32, device=xl0.device)
+        for l, (xl, ll, w) in enumerate(levels):
+            up = g * w
+            d = _take(ll.grad_fn) if xl.dtype == torch.float32 else None
+            if d is not None:                                 # a fused-pass loss: its forward already left d(loss)/d(logits) (_leave)
+                torch.mul(d, up, out=gbuf[l])
+            else:                                             # the two-call forms (their backward pass applies `up`), any other criterion
+                (d,) = torch.autograd.grad(ll, xl, grad_outputs=up.to(ll.dtype))
+                gbuf[l].copy_(d)
+        return gbuf.transpose(0, 1), None, None, None
+
+
+# the criteria a config block may name inside HipDeepSupervisionLoss ({"name": ..., options}), with or without the "Hip" prefix
+_CRITERIA = {n: c for c in (HipDiceLoss, HipGeneralizedDiceLoss, HipTverskyLoss, HipDiceCELoss, HipBCEWithLogitsLoss, HipCrossEntropyLoss,
+                            HipFocalLoss, HipDiceFocalLoss) for n in (c.__name__, c.__name__[3:])}
+
+
+class HipDeepSupervisionLoss(nn.Module):
+    """monai.losses.DeepSupervisionLoss(loss, weight_mode="exp", weights=None): sum_l w_l * loss(input[l], target) over the outputs of a
+    deeply supervised network, weights not normalised. [MONAI-memory: restated from MONAI >= 1.2 `ds_loss.py`, parity unpinned.]
+    weight_mode "exp": w_l = max(0.5 ** l, 0.0625); "same": 1; "two": 1 for level 0 and 0.5 for the others; explicit `weights` are used when
+    there are at least as many as levels. `loss`: any criterion of this module (scalar reduction).
+
+    input: a list / tuple of [N, C, D, H, W] tensors (MONAI's form), or -- an extension for HipDynUNetDS, whose training output is the
+    stack -- one 6-D tensor [N, L, C, D, H, W], unbound along dim 1; its gradient comes back in the stack's own memory order, so the
+    network's backward takes it without a copy. A 5-D tensor goes straight to `loss`. Every entry must have the target's spatial shape:
+    MONAI would down-sample the target for a coarser entry, which is not implemented (NotImplementedError)."""
+    def __init__(self, loss, weight_mode="exp", weights=None):
+        super().__init__()
+        if isinstance(loss, dict):                            # a JSON config cannot hold a module: {"name": "DiceLoss", ...its options}
+            opts = dict(loss)
+            name = opts.pop("name")
+            if name not in _CRITERIA:
+                raise ValueError(f"HipDeepSupervisionLoss: unknown criterion {name!r}; one of {sorted(_CRITERIA)}")
+            loss = _CRITERIA[name](**opts)
+        self.loss = loss
+        self.weight_mode = _option_name(weight_mode)
+        self.weights = None if weights is None else [float(w) for w in weights]
+
+    def get_weights(self, levels=1):
+        levels = max(1, levels)
+        if self.weights is not None and len(self.weights) >= levels:
+            return self.weights[:levels]
+        if self.weight_mode == "exp":
+            return [max(0.5 ** l, 0.0625) for l in range(levels)]
+        if self.weight_mode == "two":
+            return [1.0 if l == 0 else 0.5 for l in range(levels)]
+        return [1.0] * levels                                 # "same" (and, as in MONAI, any other name)
+
+    def forward(self, input, target):
+        if isinstance(input, torch.Tensor) and input.dim() != 6:
+            return self.loss(input, target)
+        entries = list(input) if isinstance(input, (list, tuple)) else None
+        spatial = [tuple(e.shape[2:]) for e in entries] if entries is not None else [tuple(input.shape[3:])]
+        if any(s != tuple(target.shape[2:]) for s in spatial):
+            raise NotImplementedError("HipDeepSupervisionLoss: an entry's spatial shape differs from the target's (MONAI would down-sample "
+                                      "the target; up-sample the heads instead, as DynUNet does)")
+        weights = self.get_weights(len(entries) if entries is not None else input.shape[1])
+        if entries is None:
+            return _StackedFunction.apply(input, target, self, weights)
+        total = None
+        for e, w in zip(entries, weights):
+            term = self.loss(e, target) * w
+            total = term if total is None else total + term
+        return total

@@ -692,6 +692,30 @@ class Backend:
                                       ctypes.byref(dxd) if dxd is not None else None, dw.data_ptr(), _p(dbias), cout, ws.data_ptr(),
                                       ws.numel() * 4, self.stream()), "proj_bwd")
 
+    # -- deep-supervision heads ------------------------------------------------------------------------------------
+    def ds_head_fwd(self, x, w, bias, out, factor, scale=None, shift=None, slope=0.0):
+        """out [n, cout, d*factor, h*factor, w*factor] (fp32, contiguous) = nearest-up-sampled (x @ w.T + bias); x: the coarse Act, read
+        through the norm prologue (scale, shift, slope) when one is given. One slot of HipDynUNetDS's stacked output."""
+        cout = w.shape[0]
+        xd = x.desc()
+        n, d, h, w_, _ = x.shape
+        assert out.is_contiguous() and out.dtype == torch.float32 and tuple(out.shape) == (n, cout, d * factor, h * factor, w_ * factor)
+        check(self.lib.mi355_ds_head_fwd(ctypes.byref(xd), _p(scale), _p(shift), slope, w.data_ptr(), _p(bias), out.data_ptr(), cout, factor,
+                                         self.stream()), "ds_head_fwd")
+
+    def ds_head_bwd(self, x, w, dout, dx, dw, dbias, factor, scale=None, shift=None, slope=0.0):
+        """dout: the slot's gradient (ds_head_fwd's `out` layout). dw [cout, cin] and dbias [cout] (or None) are written; wT pool(dout) is
+        ADDED to the Act dx (None: not wanted)."""
+        cout = w.shape[0]
+        xd = x.desc()
+        dxd = dx.desc() if dx is not None else None
+        n, d, h, w_, _ = x.shape
+        assert dout.is_contiguous() and dout.dtype == torch.float32 and tuple(dout.shape) == (n, cout, d * factor, h * factor, w_ * factor)
+        ws = self.ws(self.lib.mi355_ds_head_scratch_bytes(ctypes.byref(xd), cout))
+        check(self.lib.mi355_ds_head_bwd(ctypes.byref(xd), _p(scale), _p(shift), slope, w.data_ptr(), dout.data_ptr(),
+                                         ctypes.byref(dxd) if dxd is not None else None, dw.data_ptr(), _p(dbias), cout, factor, ws.data_ptr(),
+                                         ws.numel() * 4, self.stream()), "ds_head_bwd")
+
     # -- sliding-window inference ---------------------------------------------------------------------------------
     def sw_accumulate(self, pred, importance, out, count, start):
         """pred [C, rd, rh, rw], importance [rd, rh, rw], out [C, D, H, W], count [D, H, W] (fp32, contiguous)."""

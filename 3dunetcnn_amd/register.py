@@ -15,9 +15,9 @@ import torch
 
 
 def register(replace=False):
-    from .dynunet import HipDynUNet
-    from .losses import (HipBCEWithLogitsLoss, HipCrossEntropyLoss, HipDiceCELoss, HipDiceFocalLoss, HipDiceLoss, HipFocalLoss,
-                         HipGeneralizedDiceLoss, HipTverskyLoss)
+    from .dynunet import HipDynUNet, HipDynUNetDS
+    from .losses import (HipBCEWithLogitsLoss, HipCrossEntropyLoss, HipDeepSupervisionLoss, HipDiceCELoss, HipDiceFocalLoss, HipDiceLoss,
+                         HipFocalLoss, HipGeneralizedDiceLoss, HipTverskyLoss)
     from .optim import HipAdam
     from .unet import HipAutocastUNet, HipAutoImplantUNet, HipUNet3D
     done = {}
@@ -25,12 +25,13 @@ def register(replace=False):
         models = importlib.import_module("unet3d.models.pytorch")
         models.HipUNet3D = HipUNet3D
         models.HipDynUNet = HipDynUNet
+        models.HipDynUNetDS = HipDynUNetDS
         models.HipAutocastUNet = HipAutocastUNet
         models.HipAutoImplantUNet = HipAutoImplantUNet
-        done["models"] = ["HipUNet3D", "HipDynUNet", "HipAutocastUNet", "HipAutoImplantUNet"]
+        done["models"] = ["HipUNet3D", "HipDynUNet", "HipDynUNetDS", "HipAutocastUNet", "HipAutoImplantUNet"]
         if replace:
             models.UNet3D = HipUNet3D
-            models.DynUNet = HipDynUNet
+            models.DynUNet = HipDynUNetDS          # the superset: HipDynUNet itself when deep_supervision is off
             models.AutocastUNet = HipAutocastUNet
             models.AutoImplantUNet = HipAutoImplantUNet
             done["models"] += ["UNet3D", "DynUNet", "AutocastUNet", "AutoImplantUNet"]
@@ -41,7 +42,7 @@ def register(replace=False):
         hip_losses = {"HipDiceLoss": HipDiceLoss, "HipDiceCELoss": HipDiceCELoss, "HipGeneralizedDiceLoss": HipGeneralizedDiceLoss,
                       "HipBCEWithLogitsLoss": HipBCEWithLogitsLoss,
                       "HipCrossEntropyLoss": HipCrossEntropyLoss, "HipFocalLoss": HipFocalLoss, "HipDiceFocalLoss": HipDiceFocalLoss,
-                      "HipTverskyLoss": HipTverskyLoss}
+                      "HipTverskyLoss": HipTverskyLoss, "HipDeepSupervisionLoss": HipDeepSupervisionLoss}
         for name, cls in hip_losses.items():
             setattr(losses, name, cls)
         done["losses"] = list(hip_losses)

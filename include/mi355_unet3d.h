@@ -277,6 +277,29 @@ int mi355_proj_bwd(const mi355_act* x, const float* in_scale, const float* in_sh
                    const float* dlogits_ncdhw, const mi355_act* dx, float* dw, float* dbias, int32_t cout,
                    void* ws, size_t ws_bytes, void* stream);
 
+/* ---- deep-supervision heads (csrc/deep_supervision.hip) ---------------------------------------- */
+/* A head of MONAI's DynUNet(deep_supervision=True): UnetOutBlock(cin -> cout, k=1, bias) on a decoder level, its result nearest-up-sampled
+ * by `factor` per axis (source index floor(dst / factor)) into one slot of the stacked network output.
+ * mi355_ds_head_fwd: x is the coarse NDHWC activation [n, d, h, w, cin] (fp32, bf16 or fp16 storage, ld >= cin), read through the same
+ *   fused prologue as mi355_proj_fwd (in_scale / in_shift [n][cin], both or neither NULL; act_slope in [0, 1]); w fp32 [cout][cin], bias
+ *   fp32 [cout] or NULL; out: contiguous fp32 [n][cout][d*factor][h*factor][w*factor], 16-byte aligned, every element written (each coarse
+ *   value to its factor^3 fine voxels, 16-byte stores where factor >= 4). One launch.
+ * mi355_ds_head_bwd: dout is the gradient of that slot (same layout), read once; dz = the sum over every factor^3 block. Writes
+ *   dw[cout][cin] = sum dz * act(x) and dbias[cout] = sum dz (dbias may be NULL) through per-workgroup partials in ws and a fixed-order
+ *   reduce: bitwise reproducible, no floating-point atomics. dx (NULL, or an NDHWC view of x's shape and storage type): wT dz, the gradient
+ *   with respect to the ACTIVATED input as in mi355_proj_bwd, is ADDED to what dx holds (fp32 sum, one rounding on store): the decoder
+ *   level already carries the gradient of the next up block. ws >= mi355_ds_head_scratch_bytes(x, cout) bytes. Two launches.
+ *   A smaller ws_bytes is MI355_STATUS_EWORKSPACE; mi355_ds_head_scratch_bytes(NULL, ...) is 0.
+ * Limits: cin a multiple of 4 and <= 320 (MONAI's default filter cap), 1 <= cout <= 8, factor a power of two in [2, 32]; in_scale and
+ * in_shift 16-byte aligned (read four channels at a time), every other fp32 pointer 4-byte aligned; anything else is
+ * MI355_STATUS_EINVAL. */
+size_t mi355_ds_head_scratch_bytes(const mi355_act* x, int32_t cout);
+int mi355_ds_head_fwd(const mi355_act* x, const float* in_scale, const float* in_shift, float act_slope, const float* w,
+                      const float* bias, float* out_ncdhw, int32_t cout, int32_t factor, void* stream);
+int mi355_ds_head_bwd(const mi355_act* x, const float* in_scale, const float* in_shift, float act_slope, const float* w,
+                      const float* dout_ncdhw, const mi355_act* dx, float* dw, float* dbias, int32_t cout, int32_t factor,
+                      void* ws, size_t ws_bytes, void* stream);
+
 /* ---- sliding-window inference ------------------------------------------------------------------ */
 /* Accumulation step of MONAI's SlidingWindowInferer, which the reference builds from config["inference"]
  * (unet3d/scripts/script_utils.py:290-293) and calls as inferer(images, model) at unet3d/train/training_utils.py:106-107 and
