@@ -105,6 +105,15 @@ SIGNATURES = {
     "mi355_ds_head_fwd": (ctypes.c_int, [POINTER(MiAct), c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
     "mi355_ds_head_bwd": (ctypes.c_int, [POINTER(MiAct), c_void_p, c_void_p, c_float, c_void_p, c_void_p, POINTER(MiAct), c_void_p, c_void_p, c_int32,
                                          c_int32, c_void_p, c_size_t, c_void_p]),
+    "mi355_res_join_fwd": (ctypes.c_int, [POINTER(MiAct), POINTER(MiAct), c_void_p, c_void_p, c_void_p, c_void_p, c_float, POINTER(MiAct), c_void_p]),
+    "mi355_res_join_scratch_bytes": (c_size_t, [POINTER(MiAct)]),
+    "mi355_res_join_bwd": (ctypes.c_int, [POINTER(MiAct), POINTER(MiAct), POINTER(MiAct), POINTER(MiAct), c_float, c_void_p, c_void_p, c_void_p,
+                                          c_void_p, POINTER(MiAct), POINTER(MiAct), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                          c_void_p]),
+    "mi355_conv1x1_s2_scratch_bytes": (c_size_t, [POINTER(MiAct), POINTER(MiAct)]),
+    "mi355_conv1x1_s2_fwd": (ctypes.c_int, [POINTER(MiAct), c_void_p, POINTER(MiAct), c_void_p]),
+    "mi355_conv1x1_s2_wgrad": (ctypes.c_int, [POINTER(MiAct), POINTER(MiAct), c_void_p, c_void_p, c_size_t, c_void_p]),
+    "mi355_conv1x1_s2_dgrad_add": (ctypes.c_int, [POINTER(MiAct), c_void_p, POINTER(MiAct), c_void_p]),
     "mi355_sw_accumulate": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
                                            c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "mi355_sw_gather": (ctypes.c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32, c_int32, c_int32,

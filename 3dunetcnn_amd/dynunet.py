@@ -8,11 +8,20 @@ and is not installed here: the structure below follows SURVEY.md section 8a-B / 
   UnetBasicBlock(ci, co, s): Conv3d(k3, stride s, pad 1, no bias) -> InstanceNorm3d(affine) -> LeakyReLU(0.01), twice
   UnetUpBlock(ci, co):       ConvTranspose3d(k2, s2, no bias) -> cat((up, skip), 1) -> UnetBasicBlock(2co, co, 1)
   UnetOutBlock:              Conv3d(filters[0] -> out_channels, k1, bias)
+  res_block=True [MONAI-memory]: every UnetBasicBlock above is a UnetResBlock(ci, co, s):
+      out = lrelu(norm1(conv1(x))); out = norm2(conv2(out)); res = norm3(conv3(x)); out = lrelu(out + res)
+      conv3 = Conv3d(k1, stride s, no bias), present when ci != co or s != 1 (every block of a DynUNet but an input block with
+      in_channels == filters[0], whose identity shortcut is refused here)
 
 MI355X execution: every conv writes its RAW output; InstanceNorm statistics are one streaming pass (mi355_gn_stats with
 G == C) and the normalise + affine + LeakyReLU is applied by the CONSUMER while it stages its LDS tile (conv prologue), so
 normalised tensors never exist in HBM. The skip-concat is a channel slice of one buffer: [0, co) = raw transposed-conv output
 (identity prologue: scale 1, shift 0, slope 1), [co, 2co) = the encoder block's raw output with its own norm prologue.
+Residual mode: a block's output is a function of two raw tensors with two sets of statistics, which no prologue expresses, so it is
+MATERIALISED: A = lrelu(sc2 r2 + sh2 + sc3 r3 + sh3) in one pass (csrc/res_block.hip, mi355_res_join_fwd), written straight into the
+encoder half of the concat buffer; every consumer (next block, transposed conv, projection, deep-supervision head) reads it IN_PLAIN and
+the concat buffer needs no per-half prologue vectors. Backward: mi355_res_join_bwd turns dA into d_r2 (in place) and d_r3 with both norms'
+parameter gradients in two passes; the stride-2 shortcut is mi355_conv1x1_s2_{fwd,wgrad,dgrad_add}, the stride-1 one the 1x1x1 conv.
 ConvTranspose3d(k2, s2) is ONE 1x1x1 GEMM with 8*co logical output channels whose epilogue scatters depth-to-space
 (MI355_OUT_D2S); its dgrad / wgrad read the fine gradient through the space-to-depth view (MI355_IN_S2D / OUT_D2S).
 """
@@ -52,11 +61,25 @@ class _BasicBlock(nn.Module):
         self.stride = stride
 
 
+class _ResBlock(nn.Module):
+    """monai UnetResBlock with cin != cout or stride != 1 (registration order: conv1, conv2, norm1, norm2, conv3, norm3). [MONAI-memory]"""
+
+    def __init__(self, cin, cout, stride):
+        super().__init__()
+        self.conv1 = _Conv(nn.Conv3d(cin, cout, 3, stride=stride, padding=1, bias=False))
+        self.conv2 = _Conv(nn.Conv3d(cout, cout, 3, stride=1, padding=1, bias=False))
+        self.norm1 = nn.InstanceNorm3d(cout, affine=True)
+        self.norm2 = nn.InstanceNorm3d(cout, affine=True)
+        self.conv3 = _Conv(nn.Conv3d(cin, cout, 1, stride=stride, bias=False))
+        self.norm3 = nn.InstanceNorm3d(cout, affine=True)
+        self.stride = stride
+
+
 class _UpBlock(nn.Module):
-    def __init__(self, cin, cout):
+    def __init__(self, cin, cout, block=_BasicBlock):
         super().__init__()
         self.transp_conv = _Conv(nn.ConvTranspose3d(cin, cout, 2, stride=2, bias=False))
-        self.conv_block = _BasicBlock(2 * cout, cout, 1)
+        self.conv_block = block(2 * cout, cout, 1)
 
 
 class _OutBlock(nn.Module):
@@ -101,8 +124,6 @@ class HipDynUNet(HipNetBase):
             bad.append("upsample_kernel_size other than 2 per level")
         if deep_supervision:
             bad.append("deep_supervision=True")
-        if res_block:
-            bad.append("res_block=True")
         if dropout is not None:
             bad.append("dropout")
         if trans_bias:
@@ -127,11 +148,18 @@ class HipDynUNet(HipNetBase):
         self.kernel_size, self.strides, self.upsample_kernel_size = kernel_size, strides, upsample_kernel_size
         self.filters = filters
         self.deep_supervision = False
+        self.res_block = bool(res_block)
+        if self.res_block and in_channels == filters[0]:
+            raise NotImplementedError("res_block=True with in_channels == filters[0]: the input block's shortcut is then the identity "
+                                      "(UnetResBlock without conv3 / norm3), which is not implemented")
+        if self.res_block and max(filters) > 384:
+            raise NotImplementedError("res_block=True: the 1x1x1 stride-2 shortcut convolution takes at most 384 channels (filters <= 384)")
+        block = _ResBlock if self.res_block else _BasicBlock
         # registration order == MONAI's (state_dict key order)
-        self.input_block = _BasicBlock(in_channels, filters[0], 1)
-        self.downsamples = nn.ModuleList(_BasicBlock(filters[i - 1], filters[i], 2) for i in range(1, L - 1))
-        self.bottleneck = _BasicBlock(filters[-2], filters[-1], 2)
-        self.upsamples = nn.ModuleList(_UpBlock(filters[L - 1 - k], filters[L - 2 - k]) for k in range(L - 1))
+        self.input_block = block(in_channels, filters[0], 1)
+        self.downsamples = nn.ModuleList(block(filters[i - 1], filters[i], 2) for i in range(1, L - 1))
+        self.bottleneck = block(filters[-2], filters[-1], 2)
+        self.upsamples = nn.ModuleList(_UpBlock(filters[L - 1 - k], filters[L - 2 - k], block) for k in range(L - 1))
         self.output_block = _OutBlock(filters[0], out_channels)
         self.deep_supervision_heads = nn.ModuleList()
         # DynUNet.initialize_weights: kaiming_normal_(a=0.01) on conv / transposed-conv weights, zero biases
@@ -207,6 +235,8 @@ class HipDynUNet(HipNetBase):
         return None if pad == 0 else (lambda w: F.pad(w, (0, 0, 0, 0, 0, 0, 0, pad)))
 
     def _block_fwd(self, be, blk, xin, dst, keep):
+        if self.res_block:
+            return self._res_block_fwd(be, blk, xin, dst, keep)
         n = xin.act.shape[0]
         cout = blk.norm1.num_features
         d, h, w = dst.shape[1:4]
@@ -221,7 +251,37 @@ class HipDynUNet(HipNetBase):
                     slope=SLOPE, moments=True)
         st2 = be.gn_stats(dst, cout, IN_EPS, blk.norm2.weight.data, blk.norm2.bias.data)
         dst.mom = None
-        return dict(xin=xin, r1=r1, st1=st1, r2=dst, st2=st2) if keep else dict(r2=dst, st2=st2)
+        out = _In(dst, st2[1], st2[2])
+        return dict(xin=xin, r1=r1, st1=st1, r2=dst, st2=st2, out=out) if keep else dict(out=out)
+
+    def _res_block_fwd(self, be, blk, xin, dst, keep):
+        """UnetResBlock: xin is PLAIN (a materialised A, the network input, or the concat buffer); dst receives A."""
+        x = xin.act
+        n, cout = x.shape[0], blk.norm1.num_features
+        d, h, w = dst.shape[1:4]
+        r1 = be.empty_act(n, d, h, w, cout)
+        be.conv_fwd(x, self._packed_weight(blk.conv1.conv.weight, 0, self._ci_pad(blk, x.c)), r1, 3, blk.stride, moments=True)
+        st1 = be.gn_stats(r1, cout, IN_EPS, blk.norm1.weight.data, blk.norm1.bias.data)
+        r1.mom = None
+        r2 = be.empty_act(n, d, h, w, cout)
+        be.conv_fwd(r1, self._packed_weight(blk.conv2.conv.weight, 0), r2, 3, 1, in_mode=IN_AFFINE_ACT, scale=st1[1], shift=st1[2],
+                    slope=SLOPE, moments=True)
+        st2 = be.gn_stats(r2, cout, IN_EPS, blk.norm2.weight.data, blk.norm2.bias.data)
+        r2.mom = None
+        # the shortcut reads the block input in the activations' storage type (the fp32 network input of a 16-bit network: one small cast)
+        x3 = x if x.dtype == r1.dtype else be.cast(x, r1.dtype)
+        r3 = be.empty_act(n, d, h, w, cout)
+        w3 = blk.conv3.conv.weight
+        if blk.stride == 2:
+            be.conv1x1_s2_fwd(x3, w3.data, r3)
+            be.moments(r3)                      # r3 has 1/8 of the input's voxels: its statistics are one standalone pass (DESIGN.md)
+        else:
+            be.conv_fwd(x3, self._packed_weight(w3, 0, self._ci_pad(blk, x.c)), r3, 1, moments=True)
+        st3 = be.gn_stats(r3, cout, IN_EPS, blk.norm3.weight.data, blk.norm3.bias.data)
+        r3.mom = None
+        be.res_join_fwd(r2, st2, r3, st3, dst, SLOPE)
+        out = _In(dst)
+        return dict(xin=xin, x3=x3, r1=r1, st1=st1, r2=r2, st2=st2, r3=r3, st3=st3, out=out) if keep else dict(out=out)
 
     def _forward_impl(self, x, keep):
         be = self._begin_forward()
@@ -250,7 +310,7 @@ class HipDynUNet(HipNetBase):
             dst = cats[i].slice(f[i], f[i]) if i < L - 1 else be.empty_act(n, *sizes[i], f[i])
             s = self._block_fwd(be, blk, cur, dst, keep)
             enc.append(s)
-            cur = _In(s["r2"], s["st2"][1], s["st2"][2])
+            cur = s["out"]
         ups = []
         ones = zeros = None
         # deep supervision: the logits and the K head outputs are slots of one buffer [1 + K][N][C][D][H][W]
@@ -262,19 +322,22 @@ class HipDynUNet(HipNetBase):
             cat = cats[lvl]
             be.conv_fwd(cur.act, self._packed_weight(up.transp_conv.conv.weight, 0, _tw_fwd), cat.slice(0, co), 1, out_mode=OUT_D2S,
                         **cur.kw())
-            sk = enc[lvl]["st2"]
-            ones = torch.ones(n, co, dtype=torch.float32, device=be.device)
-            zeros = torch.zeros(n, co, dtype=torch.float32, device=be.device)
-            sc = torch.cat((ones, sk[1]), 1).contiguous()
-            sh = torch.cat((zeros, sk[2]), 1).contiguous()
-            sl = torch.cat((ones[0], torch.full((co,), SLOPE, dtype=torch.float32, device=be.device))).contiguous()
-            cin_ = _In(cat, sc, sh, sl)
+            if self.res_block:                 # both halves are plain: the raw transposed conv and the encoder's materialised A
+                cin_ = _In(cat)
+            else:
+                sk = enc[lvl]["out"]
+                ones = torch.ones(n, co, dtype=torch.float32, device=be.device)
+                zeros = torch.zeros(n, co, dtype=torch.float32, device=be.device)
+                sc = torch.cat((ones, sk.scale), 1).contiguous()
+                sh = torch.cat((zeros, sk.shift), 1).contiguous()
+                sl = torch.cat((ones[0], torch.full((co,), SLOPE, dtype=torch.float32, device=be.device))).contiguous()
+                cin_ = _In(cat, sc, sh, sl)
             dst = be.empty_act(n, *sizes[lvl], co)
             s = self._block_fwd(be, up.conv_block, cin_, dst, keep)
             s["tin"] = cur
             ups.append(s)
-            cur = _In(s["r2"], s["st2"][1], s["st2"][2])
-            if 1 <= lvl <= K:                 # head lvl - 1 reads this level's activated output: raw + its norm prologue
+            cur = s["out"]
+            if 1 <= lvl <= K:                 # head lvl - 1 reads this level's activated output: raw + its norm prologue, or the plain A
                 hd = self.deep_supervision_heads[lvl - 1].conv.conv
                 be.ds_head_fwd(cur.act, hd.weight.data.reshape(self.out_channels, -1), hd.bias.data, stack[lvl], 2 ** lvl, cur.scale, cur.shift,
                                SLOPE)
@@ -291,8 +354,16 @@ class HipDynUNet(HipNetBase):
         input (Act) or None."""
         cout = blk.norm1.num_features
         r1, r2, st1, st2, xin = s["r1"], s["r2"], s["st1"], s["st2"], s["xin"]
-        be.gn_act_bwd(r2, dA2, dA2, cout, SLOPE, blk.norm2.weight.data, st2[0], st2[1], st2[2],
-                      self._gslice(blk.norm2.weight), self._gslice(blk.norm2.bias))
+        d_r3 = None
+        if self.res_block:
+            # join backward: d_r2 overwrites dA2, d_r3 is a tensor of its own; both norms' parameter gradients
+            d_r3 = be.empty_act(*r2.shape)
+            be.res_join_bwd(s["out"].act, dA2, r2, st2, blk.norm2.weight.data, s["r3"], s["st3"], blk.norm3.weight.data, dA2, d_r3,
+                            self._gslice(blk.norm2.weight), self._gslice(blk.norm2.bias), self._gslice(blk.norm3.weight),
+                            self._gslice(blk.norm3.bias), SLOPE)
+        else:
+            be.gn_act_bwd(r2, dA2, dA2, cout, SLOPE, blk.norm2.weight.data, st2[0], st2[1], st2[2],
+                          self._gslice(blk.norm2.weight), self._gslice(blk.norm2.bias))
         d_r2 = dA2
         with self._wgrad_stream(be, r1, d_r2, st1[1], st1[2]):
             be.conv_wgrad(r1, d_r2, self._gslice(blk.conv2.conv.weight), 3, 1, in_mode=IN_AFFINE_ACT, scale=st1[1], shift=st1[2], slope=SLOPE)
@@ -310,6 +381,17 @@ class HipDynUNet(HipNetBase):
                 tw = torch.empty(w1.shape[0], xin.act.c, 3, 3, 3, dtype=torch.float32, device=w1.device)
                 be.conv_wgrad(xin.act, d_r1, tw, 3, blk.stride, **xin.kw())
                 self._gslice(w1).copy_(tw[:, :w1.shape[1]])
+        if d_r3 is not None:
+            x3, w3 = s["x3"], blk.conv3.conv.weight
+            with self._wgrad_stream(be, x3, d_r3):
+                if blk.stride == 2:
+                    be.conv1x1_s2_wgrad(x3, d_r3, self._gslice(w3))
+                elif x3.c == w3.shape[1]:
+                    be.conv_wgrad(x3, d_r3, self._gslice(w3), 1, 1)
+                else:                              # zero-padded network input, as for conv1
+                    tw = torch.empty(w3.shape[0], x3.c, 1, 1, 1, dtype=torch.float32, device=w3.device)
+                    be.conv_wgrad(x3, d_r3, tw, 1, 1)
+                    self._gslice(w3).copy_(tw[:, :w3.shape[1]])
         self._flush_ready()
         if not need_dx:
             return None
@@ -317,9 +399,19 @@ class HipDynUNet(HipNetBase):
         dAin = be.empty_act(n, d, h, w, cin, dtype=xin.act.dtype)          # a tensor's gradient is stored like the tensor
         wp = self._packed_weight(blk.conv1.conv.weight, 1, self._ci_pad(blk, cin))
         if blk.stride == 1:
+            if d_r3 is not None:
+                # stride-1 shortcut (input block, decoder blocks: no skip gradient arrives here): its dgrad is the 1x1x1 conv, carried into
+                # conv1's dgrad through the residual epilogue
+                assert dx_residual is None
+                dx_residual = be.empty_act(n, d, h, w, cin, dtype=d_r3.dtype)
+                be.conv_fwd(d_r3, self._packed_weight(blk.conv3.conv.weight, 1, self._ci_pad(blk, cin)), dx_residual, 1)
+                if dx_residual.dtype != dAin.dtype:
+                    dx_residual = be.cast(dx_residual, dAin.dtype)
             be.conv_fwd(d_r1, wp, dAin, 3, 1, residual=dx_residual)
         else:
             be.conv_fwd(d_r1, wp, dAin, 3, 1, pad=1, in_mode=IN_ZERO_INSERT, residual=dx_residual, out_dhw=(d, h, w))
+            if d_r3 is not None:                   # after conv1's dgrad has written dAin: one voxel in eight gets the shortcut's share added
+                be.conv1x1_s2_dgrad_add(d_r3, blk.conv3.conv.weight.data, dAin)
         return dAin
 
     def _backward_impl_body(self, be, saved, dlogits, need_dx):
@@ -350,9 +442,9 @@ class HipDynUNet(HipNetBase):
                 # dA holds the gradient from the finer up block; the head adds its own before this level's norm backward consumes the sum.
                 # On the launch stream, not the weight-gradient side stream: the kernel that writes dw / dbias is the one that adds to dA
                 hd = self.deep_supervision_heads[lvl - 1].conv.conv
-                be.ds_head_bwd(s["r2"], hd.weight.data.reshape(self.out_channels, -1), dstack[lvl], dA,
-                               self._gslice(hd.weight).view(self.out_channels, -1), self._gslice(hd.bias), 2 ** lvl, s["st2"][1], s["st2"][2],
-                               SLOPE)
+                o = s["out"]
+                be.ds_head_bwd(o.act, hd.weight.data.reshape(self.out_channels, -1), dstack[lvl], dA,
+                               self._gslice(hd.weight).view(self.out_channels, -1), self._gslice(hd.bias), 2 ** lvl, o.scale, o.shift, SLOPE)
             dcat = self._block_bwd(be, up.conv_block, s, dA, True)
             d_up, d_skip[lvl] = dcat.slice(0, co), dcat.slice(co, co)
             tin = s["tin"]                                  # activated input of the transposed conv (raw + prologue)

@@ -716,6 +716,42 @@ class Backend:
                                          ctypes.byref(dxd) if dxd is not None else None, dw.data_ptr(), _p(dbias), cout, factor, ws.data_ptr(),
                                          ws.numel() * 4, self.stream()), "ds_head_bwd")
 
+    # -- residual blocks (csrc/res_block.hip) ----------------------------------------------------------------------
+    def res_join_fwd(self, r2, st2, r3, st3, a, slope):
+        """a = lrelu(norm2(r2) + norm3(r3)) from the two raw tensors and their statistics st_b = (mean_rstd, scale, shift) of gn_stats."""
+        d2, d3, da = r2.desc(), r3.desc(), a.desc()
+        check(self.lib.mi355_res_join_fwd(ctypes.byref(d2), ctypes.byref(d3), st2[1].data_ptr(), st2[2].data_ptr(), st3[1].data_ptr(),
+                                          st3[2].data_ptr(), slope, ctypes.byref(da), self.stream()), "res_join_fwd")
+
+    def res_join_bwd(self, a, dA, r2, st2, gamma2, r3, st3, gamma3, d_r2, d_r3, dgamma2, dbeta2, dgamma3, dbeta3, slope):
+        """Backward of res_join_fwd through both InstanceNorms: d_r2 (may be dA itself: overwritten in place) and d_r3 (a tensor of its own),
+        dgamma / dbeta of both norms (written)."""
+        ad, dad, d2, d3, o2, o3 = a.desc(), dA.desc(), r2.desc(), r3.desc(), d_r2.desc(), d_r3.desc()
+        ws = self.ws(self.lib.mi355_res_join_scratch_bytes(ctypes.byref(ad)))
+        check(self.lib.mi355_res_join_bwd(ctypes.byref(ad), ctypes.byref(dad), ctypes.byref(d2), ctypes.byref(d3), slope, _p(gamma2),
+                                          st2[0].data_ptr(), _p(gamma3), st3[0].data_ptr(), ctypes.byref(o2), ctypes.byref(o3),
+                                          dgamma2.data_ptr(), dbeta2.data_ptr(), dgamma3.data_ptr(), dbeta3.data_ptr(), ws.data_ptr(),
+                                          ws.numel() * 4, self.stream()), "res_join_bwd")
+
+    def conv1x1_s2_fwd(self, x, w, y):
+        """y[n, z, y, x, :] = w x[n, 2z, 2y, 2x, :]; w: the fp32 OIDHW weight [cout, cin, 1, 1, 1] (or [cout, cin]), contiguous."""
+        assert w.is_contiguous() and w.dtype == torch.float32 and w.numel() == x.c * y.c
+        xd, yd = x.desc(), y.desc()
+        check(self.lib.mi355_conv1x1_s2_fwd(ctypes.byref(xd), w.data_ptr(), ctypes.byref(yd), self.stream()), "conv1x1_s2_fwd")
+
+    def conv1x1_s2_wgrad(self, x, dy, dw):
+        assert dw.is_contiguous() and dw.dtype == torch.float32 and dw.numel() == x.c * dy.c
+        xd, dyd = x.desc(), dy.desc()
+        ws = self.ws(self.lib.mi355_conv1x1_s2_scratch_bytes(ctypes.byref(xd), ctypes.byref(dyd)))
+        check(self.lib.mi355_conv1x1_s2_wgrad(ctypes.byref(xd), ctypes.byref(dyd), dw.data_ptr(), ws.data_ptr(), ws.numel() * 4, self.stream()),
+              "conv1x1_s2_wgrad")
+
+    def conv1x1_s2_dgrad_add(self, dy, w, dx):
+        """dx[n, 2z, 2y, 2x, :] += wT dy[n, z, y, x, :]; the other voxels of dx are not touched."""
+        assert w.is_contiguous() and w.dtype == torch.float32 and w.numel() == dx.c * dy.c
+        dyd, dxd = dy.desc(), dx.desc()
+        check(self.lib.mi355_conv1x1_s2_dgrad_add(ctypes.byref(dyd), w.data_ptr(), ctypes.byref(dxd), self.stream()), "conv1x1_s2_dgrad_add")
+
     # -- sliding-window inference ---------------------------------------------------------------------------------
     def sw_accumulate(self, pred, importance, out, count, start):
         """pred [C, rd, rh, rw], importance [rd, rh, rw], out [C, D, H, W], count [D, H, W] (fp32, contiguous)."""

@@ -300,6 +300,46 @@ int mi355_ds_head_bwd(const mi355_act* x, const float* in_scale, const float* in
                       const float* dout_ncdhw, const mi355_act* dx, float* dw, float* dbias, int32_t cout, int32_t factor,
                       void* ws, size_t ws_bytes, void* stream);
 
+/* ---- residual blocks of DynUNet (csrc/res_block.hip) ------------------------------------------- */
+/* MONAI's UnetResBlock (DynUNet(res_block=True)), restated from memory:
+ *   out = lrelu(norm1(conv1(x))); out = norm2(conv2(out)); res = norm3(conv3(x)); out = lrelu(out + res)
+ * conv3 is 1x1x1 with conv1's stride. r2 = conv2's and r3 = conv3's RAW outputs, norm_b the InstanceNorm whose statistics mi355_gn_stats
+ * (groups == c) left as mean_rstd_b [n][c][2] and scale_b / shift_b [n][c]. Every view of one call has the same (n, d, h, w, c) and the same
+ * storage type (fp32, bf16 or fp16; a mixed set is MI355_STATUS_EUNSUPPORTED), any ld >= c and channel offset; arithmetic is fp32; c <= 1024.
+ * mi355_res_join_fwd: A = lrelu(scale2[n,c] * r2 + shift2[n,c] + scale3[n,c] * r3 + shift3[n,c], act_slope), act_slope in [0, 1]. Reads r2
+ *   and r3 once, writes A once. One launch. scale / shift 16-byte aligned.
+ * mi355_res_join_bwd: with g = dA * (A > 0 ? 1 : act_slope) -- the sign of A is the sign of the pre-activation, the slope being positive;
+ *   scale and shift are therefore not needed -- writes, for b in {2, 3},
+ *     d_r_b = gamma_b rstd_b (g - mean(g) - xhat_b mean(g xhat_b)),  xhat_b = (r_b - mean_b) rstd_b,  means over the (n, c) plane,
+ *     dgamma_b[c] = sum_n sum(g xhat_b),  dbeta_b[c] = sum_n sum(g)             (gamma_b NULL: ones).
+ *   Pass 1 reads A, dA, r2, r3 and leaves per-workgroup sums (g, g xhat2, g xhat3) in ws; a small launch combines them in a fixed order (in
+ *   double: no floating-point atomics, bitwise reproducible) into per-(n, c) coefficients and the four parameter gradients; pass 2 reads A,
+ *   dA, r2, r3 again and writes d_r2 and d_r3: 8 tensor reads, 2 writes, three launches. d_r2 MAY be dA itself (same pointer and ld: the
+ *   gradient is overwritten in place, which is what the engine does); d_r3 must not overlap anything the call reads.
+ *   ws: 16-byte aligned, >= mi355_res_join_scratch_bytes(a) bytes, else MI355_STATUS_EWORKSPACE; the query of NULL is 0.
+ *
+ * The shortcut of the down-sampling blocks, Conv3d(cin -> cout, k = 1, stride = 2, no bias): y[n, z, y, x, :] = W x[n, 2z, 2y, 2x, :].
+ * x is read PLAIN (in residual mode every block input is a materialised A). w: the fp32 OIDHW weight [cout][cin], 16-byte aligned. Limits:
+ * cin and cout multiples of 4 (the view rule) and <= 384, past that MI355_STATUS_EUNSUPPORTED; the extents of the fine tensor even and twice
+ * the coarse one's, else MI355_STATUS_EINVAL; both views of one storage type. fp32 fma arithmetic in every precision mode.
+ * mi355_conv1x1_s2_fwd: reads the even voxels of x (one in eight) and w, writes y. One launch.
+ * mi355_conv1x1_s2_wgrad: dw[cout][cin] = sum over (n, z, y, x) of dy[.., co] * x[n, 2z, 2y, 2x, ci]; reads dy and the even voxels of x once
+ *   per 64 x 64 tile of dw; per-split partial matrices in ws, summed in a fixed order (double). Two launches.
+ *   ws: 16-byte aligned, >= mi355_conv1x1_s2_scratch_bytes(x, dy) bytes (at most 16 MiB), else MI355_STATUS_EWORKSPACE.
+ * mi355_conv1x1_s2_dgrad_add: dx[n, 2z, 2y, 2x, :] += WT dy[n, z, y, x, :] -- ADDED (fp32 sum, one rounding on store) to what the even voxels
+ *   of dx hold (run it after conv1's dgrad has written dx); the other seven voxels in eight are not touched; each voxel by one thread. One launch. */
+int mi355_res_join_fwd(const mi355_act* r2, const mi355_act* r3, const float* scale2, const float* shift2, const float* scale3,
+                       const float* shift3, float act_slope, const mi355_act* a, void* stream);
+size_t mi355_res_join_scratch_bytes(const mi355_act* a);
+int mi355_res_join_bwd(const mi355_act* a, const mi355_act* da, const mi355_act* r2, const mi355_act* r3, float act_slope,
+                       const float* gamma2, const float* mean_rstd2, const float* gamma3, const float* mean_rstd3,
+                       const mi355_act* d_r2, const mi355_act* d_r3, float* dgamma2, float* dbeta2, float* dgamma3, float* dbeta3,
+                       void* ws, size_t ws_bytes, void* stream);
+size_t mi355_conv1x1_s2_scratch_bytes(const mi355_act* x, const mi355_act* dy);
+int mi355_conv1x1_s2_fwd(const mi355_act* x, const float* w, const mi355_act* y, void* stream);
+int mi355_conv1x1_s2_wgrad(const mi355_act* x, const mi355_act* dy, float* dw, void* ws, size_t ws_bytes, void* stream);
+int mi355_conv1x1_s2_dgrad_add(const mi355_act* dy, const float* w, const mi355_act* dx, void* stream);
+
 /* ---- sliding-window inference ------------------------------------------------------------------ */
 /* Accumulation step of MONAI's SlidingWindowInferer, which the reference builds from config["inference"]
  * (unet3d/scripts/script_utils.py:290-293) and calls as inferer(images, model) at unet3d/train/training_utils.py:106-107 and
